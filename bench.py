@@ -24,7 +24,8 @@ timed region and exactly K decode steps are timed.
   payload, as the reference ships the model dtype) captured inside every rank's
   decode graph, the last shard returns it to the master.  Batch-1 layer sharding
   does not add throughput (one token walks the ranks in sequence): the curve is
-  strong scaling of ONE decode stream.  Extra fields (``--no-extras`` skips them):
+  strong scaling of ONE decode stream.  Extra fields (only with ``--full``, see below;
+  ``--no-extras`` skips them there):
   ``tp`` = tensor parallelism (beyond the reference: every rank streams 1/N of
   every layer, device-side all-reduces over xGMI), ``pp_streams`` = the layer-
   sharded pipeline with N independent batch-1 sequences in flight (one per stage:
@@ -34,6 +35,14 @@ timed region and exactly K decode steps are timed.
 * Timing: W untimed warm-up steps, then exactly K decode steps bracketed by a
   device synchronise on both sides on rank 0 (parallel/native_bench.py: in a
   multi-rank run every token walks all ranks inside the replays rank 0 paces).
+* A plain run does only what the headline needs: set up, warm up, time the K steps,
+  print the line.  ``--full`` adds every sub-record next to it: ``llama3_70b.single``
+  and ``sd.sdxl_1024`` (the SDXL seconds per diffusion step) at N = 1, ``tp`` /
+  ``pp_streams`` / ``llama3_70b`` / the split-UNet ``sd`` at N > 1, and the best-of-three
+  warm TTFT (a plain run reports the warm-up generation's prefill).
+* ``--dump-outputs DIR`` writes what the timed steps returned, the K token ids of every
+  stream, as ``DIR/tokens.npy`` (float32 [streams, K]); weights and prompt are seeded,
+  so the same arguments give the same inputs in every run.
 
 Weights are random-init of the named architecture (no network, no checkpoints);
 EOS is ignored so exactly K tokens are generated.
@@ -67,6 +76,15 @@ def _args(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="N>1 transport: nccl (= RCCL over xGMI) or host-staged gloo (tests)")
     ap.add_argument("--dump-tokens", default=None, help="write generated token ids (JSON)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what they returned as DIR/<name>.npy: "
+                         "tokens.npy, float32 [streams, steps], the token ids of the timed "
+                         "decode steps (seeded weights and prompt: identical from run to run)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the tp / pp_streams / 70B / "
+                         "SD sub-records (--extras, --no-extras, --no-sd and --tiny-extras select "
+                         "among them) and the best-of-three warm TTFT; off by default, a plain "
+                         "run sets up, warms up, times --steps decode steps and prints the line")
     ap.add_argument("--streams", type=int, default=1,
                     help="N>1: concurrent sequences in the pipeline (1 = cake's single-sequence "
                          "pipeline, the headline; S > 1 = aggregate throughput of S sequences)")
@@ -167,6 +185,7 @@ def bench_cpu_single(a) -> None:
     if a.dump_tokens:
         with open(a.dump_tokens, "w") as f:
             json.dump([toks], f)
+    _dump_outputs(a)
     xs = sorted(times)
     _emit(a, a.steps / dt, dt * 1e3 / a.steps, xs[len(xs) // 2], xs[min(len(xs) - 1, int(0.99 * len(xs)))],
           1, {"device": "cpu"})
@@ -245,7 +264,7 @@ def _summary(r: dict | None) -> dict | None:
 def _extras_on(a) -> bool:
     """Sub-records next to the headline: the full default bench (8B headline on the
     GPU), or the tiny presets with --tiny-extras (CPU plumbing)."""
-    if a.no_extras:
+    if not a.full or a.no_extras:
         return False
     return bool(a.tiny_extras) or (not a.cpu and a.model == "llama3-8b")
 
@@ -272,6 +291,21 @@ def _want(a, name: str) -> bool:
     return "all" in sel or name in sel
 
 
+def _dump_outputs(a) -> None:
+    """--dump-outputs DIR: what the timed steps returned to their caller, the token ids of
+    the --steps timed decode steps of every stream, as DIR/tokens.npy (float32: ids are
+    below 2^24).  Every engine records its token history (prompt, first token, warm-up,
+    timed steps) for --dump-tokens; the timed steps are its last --steps entries."""
+    if not a.dump_outputs:
+        return
+    import numpy as np
+    with open(a.dump_tokens) as f:
+        hist = json.load(f)
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    np.save(os.path.join(a.dump_outputs, "tokens.npy"),
+            np.asarray([h[-a.steps:] for h in hist], dtype=np.float32))
+
+
 def _native(a) -> bool:
     # the native engine's hops / all-reduces are the in-graph device IPC ones: a run that
     # asks for the host-staged torch.distributed transports stays on the Python engines
@@ -286,8 +320,9 @@ def bench_single(a) -> None:
     else:
         measure = measure_single
     r = measure(a, a.model, a.steps, a.warmup, a.dump_tokens)
+    _dump_outputs(a)
     extra = {k: v for k, v in r.items() if k not in _MAIN_KEYS}
-    if not a.no_extras and a.model == "llama3-8b" and _want(a, "70b_single"):
+    if a.full and not a.no_extras and a.model == "llama3-8b" and _want(a, "70b_single"):
         # the 70B point on one GPU (135 GB of bf16 weights in 288 GB of HBM)
         try:
             extra["llama3_70b"] = {"single": _summary(measure(a, "llama3-70b", a.steps,
@@ -333,6 +368,8 @@ def bench_multi(a) -> None:
             measure.update(pp=native_pp, tp=native_tp)
         head_fn = measure[a.parallel] if a.streams == 1 else measure_pipeline
         head = head_fn(a, env, a.model, a.steps, a.warmup, a.dump_tokens)
+        if env.rank == 0:
+            _dump_outputs(a)
         extra = {}
         for path, model, mode in _extra_runs(a):
             if mode == "pp_streams" and (env.world == 1 or a.streams == env.world):
@@ -446,6 +483,16 @@ def main(argv=None) -> int:
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a, argv)
+    if a.dump_outputs and not a.dump_tokens:
+        # --dump-outputs reads the history the engines write for --dump-tokens
+        import tempfile
+        with tempfile.TemporaryDirectory(prefix="cake_bench_out_") as d:
+            a.dump_tokens = os.path.join(d, "tokens.json")
+            return _run(a, world)
+    return _run(a, world)
+
+
+def _run(a, world: int) -> int:
     # under torchrun (WORLD_SIZE set) the distributed path runs even at N = 1
     if world > 1 or a.gpus > 1 or "WORLD_SIZE" in os.environ:
         bench_multi(a)

@@ -69,8 +69,10 @@ def _timed(eng, cfg, a, steps: int, warmup: int, dump_tokens=None) -> dict:
     kw = dict(temperature=0.0, repeat_penalty=a.repeat_penalty, repeat_last_n=a.repeat_last_n,
               eos_ids=[])  # EOS ignored: exactly K tokens
     eng.generate(prompt, 2, **kw)               # cold: first launches + graph capture
-    # TTFT: the best of three warm prefills (one sample swings by ~1 ms with the clock)
-    pre = [eng.generate(prompt, 1, **kw).prefill_s for _ in range(2)]
+    # TTFT: the warm-up generation's prefill; with --full the best of three warm prefills
+    # (one sample swings by ~1 ms with the clock)
+    pre = [eng.generate(prompt, 1, **kw).prefill_s
+           for _ in range(2 if getattr(a, "full", False) else 0)]
     warm = eng.generate(prompt, 1 + warmup, **kw)  # prefill + first token + W warm-up steps
     torch.cuda.synchronize()
     t0 = time.perf_counter()

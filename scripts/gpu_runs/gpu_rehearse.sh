@@ -12,7 +12,7 @@ N=${1:-2}
 (while sleep 50; do date >> $OUT/heartbeat_n$N; done) & HB=$!
 start=$(date +%s)
 timeout -k 10 ${2:-1050} python -m torch.distributed.run --nnodes 1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $N --steps 20 --warmup 5 --dist-backend gloo \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus $N --full --steps 20 --warmup 5 --dist-backend gloo \
   > $OUT/bench_n$N.log 2>&1
 rc=$?
 end=$(date +%s)

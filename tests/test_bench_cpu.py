@@ -69,14 +69,35 @@ def test_self_launch_tensor_parallel(tmp_path):
     assert len(toks) == 9 + 1 + 2 + 5   # prompt + first token + warmup + timed steps
 
 
+def test_dump_outputs_and_plain_run_has_no_sub_records(tmp_path):
+    """--dump-outputs DIR writes what the timed steps returned (tokens.npy: float32
+    [streams, steps], the last --steps ids of the --dump-tokens history), the same from run
+    to run and under layer sharding; without --full no sub-record runs, even where
+    --tiny-extras names them."""
+    import numpy as np
+    r1 = _run(["--dump-outputs", str(tmp_path / "a"), "--dump-tokens", str(tmp_path / "a.json")])
+    assert r1.returncode == 0, r1.stderr[-2000:]
+    a = np.load(tmp_path / "a" / "tokens.npy")
+    hist = json.loads((tmp_path / "a.json").read_text())
+    assert a.dtype == np.float32 and a.shape == (1, 5)
+    assert a[0].tolist() == [float(t) for t in hist[0][-5:]]
+    r2 = _run(["--gpus", "2", "--tiny-extras", "--dump-outputs", str(tmp_path / "b")])
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    j = _json(r2)
+    assert j["steps"] == 5 and j["ms_per_step"] > 0
+    assert not {"tp", "pp_streams", "llama3_70b", "sd"} & set(j), sorted(j)
+    assert sorted(p.name for p in (tmp_path / "b").iterdir()) == ["tokens.npy"]
+    assert np.array_equal(np.load(tmp_path / "b" / "tokens.npy"), a)
+
+
 def test_eight_ranks_full_extras_tiny():
-    """The full default N>1 bench path at N = 8 on the tiny presets (--tiny-extras):
+    """The full default N>1 bench path at N = 8 on the tiny presets (--full --tiny-extras):
     headline pp, tp (skipped: 8 does not divide tiny-kv2's KV heads), pp_streams,
     the 70B pp / tp sub-records and the split-UNet SD sub-record — the code the
     driver's 8-GPU run executes, end to end on gloo."""
     import time
     t0 = time.time()
-    r = _run(["--gpus", "8", "--tiny-extras", "--sd-steps", "2"], timeout=600)
+    r = _run(["--gpus", "8", "--full", "--tiny-extras", "--sd-steps", "2"], timeout=600)
     wall = time.time() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json(r)
@@ -98,10 +119,10 @@ def test_split_sd_matches_single_rank():
     gloo, one OpenMP thread per rank): the packed hops carry the feature map and the
     skip stack exactly."""
     env = {"OMP_NUM_THREADS": "1"}
-    r1 = _run(["--tiny-extras", "--sd-steps", "2"], env={**env, "WORLD_SIZE": "1", "RANK": "0",
-                                                           "MASTER_PORT": "29731"}, timeout=300)
+    r1 = _run(["--full", "--tiny-extras", "--sd-steps", "2"],
+              env={**env, "WORLD_SIZE": "1", "RANK": "0", "MASTER_PORT": "29731"}, timeout=300)
     assert r1.returncode == 0, r1.stderr[-3000:]
-    r3 = _run(["--gpus", "3", "--tiny-extras", "--sd-steps", "2"], env=env, timeout=400)
+    r3 = _run(["--gpus", "3", "--full", "--tiny-extras", "--sd-steps", "2"], env=env, timeout=400)
     assert r3.returncode == 0, r3.stderr[-3000:]
     a = _json(r1)["sd"]["sdxl_tiny_split"]
     b = _json(r3)["sd"]["sdxl_tiny_split"]

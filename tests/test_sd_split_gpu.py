@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _split(n: int, extra_env=None) -> dict:
     args = ["bench.py", "--model", "tiny", "--steps", "3", "--warmup", "2", "--prompt-len", "9",
-            "--max-seq", "128", "--tiny-extras", "--extras", "sd", "--sd-steps", "3"]
+            "--max-seq", "128", "--full", "--tiny-extras", "--extras", "sd", "--sd-steps", "3"]
     # fixed convolution plans: the autotuner may pick a different (differently rounded)
     # variant per process, which would make bitwise equality across runs luck
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CAKE_HOP_TIMEOUT="30",
