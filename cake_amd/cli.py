@@ -88,6 +88,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--hop-dtype", choices=["f32", "bf16"], default="f32",
       help="hidden-state payload of an ipc hop (bf16 = the reference's 16-bit transport)")
     a("--max-seq-len", type=int, default=4096)
+    a("--weight-dtype", choices=["model", "fp8"], default="model",
+      help="native Llama engine: fp8 = the per-layer projections as e4m3 codes with one "
+           "scale per row, quantised on load (not with --parallel tp); model = --dtype")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -115,6 +118,34 @@ def run_parsed(opts: dict) -> int:
     return _run(args)
 
 
+FP8_NEEDS_NATIVE = ("--weight-dtype fp8 is served by the native Llama engine only (a GPU, "
+                    "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
+                    "take the Python path, which has no fp8 weights: refusing rather than "
+                    "running 16-bit")
+
+
+def fp8_refusal(ctx) -> str | None:
+    """Why this context cannot run ``--weight-dtype fp8`` (None: it can, or fp8 is off).
+    Every Python engine path refuses; none silently runs 16-bit."""
+    if getattr(ctx, "weight_dtype", "model") != "fp8":
+        return None
+    a = ctx.args
+    if ctx.model_type != "text-model":
+        return "--weight-dtype fp8 applies to the text model only"
+    from .models.llama3.native_generator import native_eligible
+    if not native_eligible(ctx):
+        return FP8_NEEDS_NATIVE
+    if a.transport == "rccl":
+        if getattr(a, "parallel", "pp") == "tp":
+            return "--weight-dtype fp8 is not supported with --parallel tp yet"
+        if getattr(a, "hop", "ipc") != "ipc":
+            return FP8_NEEDS_NATIVE
+    elif a.mode == "worker" or a.transport == "loopback":
+        # python -m cake_amd.cli workers are the Python worker (cake-cli hosts the native one)
+        return FP8_NEEDS_NATIVE
+    return None
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -123,6 +154,10 @@ def _run(args) -> int:
     setup_logging(args.log_level)
     from .context import Context
     ctx = Context.from_args(args)
+    why = fp8_refusal(ctx)
+    if why:
+        print(f"cake-cli: {why}", file=sys.stderr)
+        return 2
     if args.transport == "rccl":
         from .parallel.rccl_roles import run_rccl
         run_rccl(ctx)

@@ -41,6 +41,7 @@ class Context:
     sampling: SamplingConfig = field(default_factory=SamplingConfig)
     max_seq_len: int = 4096
     no_graph: bool = False
+    weight_dtype: str = "model"  # --weight-dtype: "fp8" = native engine, e4m3 projections
 
     @classmethod
     def from_args(cls, args) -> "Context":
@@ -65,7 +66,8 @@ class Context:
         return cls(args=args, mode=args.mode, name=args.name, address=args.address,
                    model_path=Path(args.model), model_type=args.model_type, topology=topology,
                    device=device, dtype=dtype, sampling=sampling, max_seq_len=args.max_seq_len,
-                   no_graph=getattr(args, "no_graph", False))
+                   no_graph=getattr(args, "no_graph", False),
+                   weight_dtype=getattr(args, "weight_dtype", "model") or "model")
 
 
 def hbm_mib(device=None) -> dict:

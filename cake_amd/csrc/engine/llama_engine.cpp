@@ -90,6 +90,21 @@ int cake_gemv_x16(int dt, const void* x, const void* w, int K, int N, float* out
                   hipStream_t st);
 int cake_swiglu(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
                 const void* wu, int K, int I, void* act, hipStream_t st);
+// FP8 e4m3fn weight-only projections (quant_fp8.hip, gemv_w8*.hip)
+int cake_quant_rows_fp8(int dt, const void* w16, int N, int K, void* w8, float* scale,
+                        hipStream_t st);
+int cake_dequant_rows_fp8(int dt, const void* w8, const float* scale, int N, int K, void* out16,
+                          hipStream_t st);
+int cake_qkv_rope_w8(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
+                     const void* wk, const void* wv, const float* sq, const float* sk,
+                     const float* sv, int K, int nh, int nkv, int hd, const float* inv_freq,
+                     const int* pos, float* q_out, void* kcache, void* vcache, int S,
+                     hipStream_t st);
+int cake_swiglu_w8(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
+                   const void* wu, const float* sg, const float* su, int K, int I, void* act,
+                   hipStream_t st);
+int cake_gemv_x16_w8(int dt, const void* x, const void* w, const float* scale, int K, int N,
+                     float* out, int accumulate, hipStream_t st);
 int cake_gemv_norm_f32(int dt, const float* resid, const void* norm_w, float eps, const void* w,
                        int K, int N, float* out, hipStream_t st);
 int cake_head_select(int dt, const float* resid, const void* norm_w, float eps, const void* w,
@@ -288,6 +303,11 @@ void trace(int rank, const std::string& what) {
   std::fflush(stderr);
 }
 
+// refused before any network or GPU work, so a caller can never hang on it
+const char* const kNoFp8TP =
+    "fp8 weights (weight_fmt 1) are not supported with tensor parallelism yet: open the "
+    "tensor-parallel engine with weight_fmt 0";
+
 Json msg(const char* cmd) {
   Json j = Json::object();
   j.set("cmd", Json::string(cmd));
@@ -302,8 +322,11 @@ class Llama {
   Llama(const std::string& dir, const CakeEngineOpts& o, const CakePipeOpts* pp = nullptr,
         const std::vector<int>* layers = nullptr, const CakeTPOpts* tp = nullptr,
         const CakeRemoteOpts* remote = nullptr)
-      : dt_(o.dtype), dev_(o.device), init_(o.init), seed_(o.seed) {
+      : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), seed_(o.seed) {
     if (dt_ != 0 && dt_ != 1) throw Error("dtype must be 0 (bf16) or 1 (f16)");
+    if (wfmt_ != 0 && wfmt_ != 1)
+      throw Error("weight_fmt must be 0 (model dtype) or 1 (fp8 e4m3 projections)");
+    if (wfmt_ != 0 && tp) throw Error(kNoFp8TP);
     if (init_ != 0 && init_ != 1) throw Error("init must be 0 (checkpoint) or 1 (random)");
     if (tp) {
       tp_ = tp->world;
@@ -347,6 +370,8 @@ class Llama {
       lc_.V = vr.second - vr.first;
       if (lc_.I % 8 || (lc_.nh * cfg_.hd) % 8) throw Error("tensor-parallel slice not 8-aligned");
     }
+    if (wfmt_ == 1 && (cfg_.H % 16 || (cfg_.nh * cfg_.hd) % 16 || cfg_.I % 16))
+      throw Error("fp8 weights need hidden, attention and intermediate widths divisible by 16");
     if (layers) {  // a TCP worker: the topology node's layers, no embedding / head
       owned_ = *layers;
       std::sort(owned_.begin(), owned_.end());
@@ -396,6 +421,12 @@ class Llama {
     if (!layers) plan_walk();
     planner_.load(pkg_dir() + "/ops/gemm_tuned.json");
     load_weights(dir);
+    // one line per open: what the weights are and what they occupy
+    std::fprintf(stderr, "cake engine: weights %s, %lld bytes on device (rank %d, %d layers)\n",
+                 wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
+                                        : "fp8 e4m3 projections (f16 rest)")
+                            : (dt_ == 0 ? "bf16" : "f16"),
+                 (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
     {
@@ -454,6 +485,7 @@ class Llama {
 
   const Cfg& cfg() const { return cfg_; }
   int max_seq() const { return S_; }
+  int64_t weight_bytes() const { return weight_bytes_; }
 
   void prefill_logits(const int32_t* prompt, int T, float* host_logits) {
     hip_check(hipSetDevice(dev_), "hipSetDevice");
@@ -702,7 +734,12 @@ class Llama {
   }
 
  private:
-  struct LayerW { void *ln1, *wqkv, *wo, *ln2, *wgu, *wd; };
+  // weight_fmt 1: wqkv / wo / wgu / wd hold e4m3 codes, s* their f32 row scales (packed as
+  // the rows are: q|k|v, gate|up)
+  struct LayerW {
+    void *ln1, *wqkv, *wo, *ln2, *wgu, *wd;
+    float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
+  };
   struct Mode {
     bool fused = true;  // greedy with the fused head_select tail
     bool greedy = true;
@@ -717,6 +754,12 @@ class Llama {
   };
 
   int dt_, dev_, init_ = 0;
+  int wfmt_ = 0;               // CakeEngineOpts.weight_fmt
+  int64_t weight_bytes_ = 0;   // device weight allocations of this rank
+  // weight_fmt 1: 16-bit scratch for the largest projection — the loader fills it before
+  // each quantise (the 16-bit copy is never kept), prefill dequantises into it before
+  // each GEMM
+  uint16_t* w16_ = nullptr;
   bool forced_ = false;  // teacher-forcing steps: the head writes full logits
   // fused decode attention + o_proj (attn_oproj.hip) for one-split live lengths: the
   // short-context graph bucket and eager steps at such a position
@@ -893,6 +936,37 @@ class Llama {
     hip_check(hipStreamSynchronize(st_), "sync");
   }
 
+  // a 16-bit weight tensor of n elements (counted in weight_bytes_)
+  uint16_t* walloc16(size_t n) {
+    weight_bytes_ += (int64_t)n * 2;
+    return dalloc<uint16_t>(n);
+  }
+  // where the loader writes the 16-bit rows of a projection [N, K]: the tensor's own
+  // allocation, or (weight_fmt 1) the shared scratch, sized for the largest projection
+  uint16_t* proj_stage(size_t N, size_t K) {
+    if (wfmt_ == 0) return walloc16(N * K);
+    if (!w16_) {
+      const size_t H = cfg_.H, nq = (size_t)lc_.nh * cfg_.hd, nk = (size_t)lc_.nkv * cfg_.hd;
+      const size_t I = lc_.I;
+      w16_ = dalloc<uint16_t>(std::max({(nq + 2 * nk) * H, H * nq, 2 * I * H, H * I}));
+    }
+    return w16_;
+  }
+  // keep what proj_stage's buffer now holds: as it is, or quantised into its own codes +
+  // row scales (quant_fp8.hip); the scratch is free again on return
+  void proj_keep(uint16_t* staged, size_t N, size_t K, void*& w, float*& sc) {
+    if (wfmt_ == 0) {
+      w = staged;
+      return;
+    }
+    uint8_t* w8 = dalloc<uint8_t>(N * K);
+    sc = dalloc<float>(N);
+    weight_bytes_ += (int64_t)(N * K + 4 * N);
+    k_check(cake_quant_rows_fp8(dt_, staged, (int)N, (int)K, w8, sc, st_), "quant_rows_fp8");
+    hip_check(hipStreamSynchronize(st_), "sync");
+    w = w8;
+  }
+
   // weights of this rank: all of the model, its pipeline layers, or (tensor parallel) its
   // slices — q / k / v rows of its heads, o_proj columns of its heads, gate / up rows and
   // down_proj columns of its intermediate range, lm_head rows of its vocabulary range
@@ -910,14 +984,14 @@ class Llama {
       k_check(cake_fill_normal(dt_, p, n, mean, std, key, st_), "fill_normal");
     };
     if (head_) {
-      embed_ = dalloc<uint16_t>(V * H);
+      embed_ = walloc16(V * H);
       fill(embed_, V * H, 0.f, 1.f, 1);
-      norm_ = dalloc<uint16_t>(H);
+      norm_ = walloc16(H);
       fill(norm_, H, 1.f, 0.05f, 2);
       if (c.tie && tp_ == 1) {
         lm_head_ = embed_;
       } else {
-        lm_head_ = dalloc<uint16_t>((size_t)lc_.V * H);
+        lm_head_ = walloc16((size_t)lc_.V * H);
         fill(lm_head_, (size_t)lc_.V * H, 0.f, 0.02f, 3);
       }
     }
@@ -925,18 +999,20 @@ class Llama {
     for (int l : owned_) {
       LayerW& w = layers_[local_[l]];
       const uint64_t t = 16 + 16 * (uint64_t)l;
-      w.ln1 = dalloc<uint16_t>(H);
+      // a projection [N, K]: drawn as 16-bit rows, kept or quantised (proj_keep)
+      auto proj = [&](void*& wp, float*& sp, size_t N, size_t K, uint64_t tag) {
+        uint16_t* p = proj_stage(N, K);
+        fill(p, N * K, 0.f, 0.02f, tag);
+        proj_keep(p, N, K, wp, sp);
+      };
+      w.ln1 = walloc16(H);
       fill(w.ln1, H, 1.f, 0.05f, t);
-      w.wqkv = dalloc<uint16_t>((nq + 2 * nk) * H);
-      fill(w.wqkv, (nq + 2 * nk) * H, 0.f, 0.02f, t + 1);
-      w.wo = dalloc<uint16_t>(H * nq);
-      fill(w.wo, H * nq, 0.f, 0.02f, t + 2);
-      w.ln2 = dalloc<uint16_t>(H);
+      proj(w.wqkv, w.sqkv, nq + 2 * nk, H, t + 1);
+      proj(w.wo, w.so, H, nq, t + 2);
+      w.ln2 = walloc16(H);
       fill(w.ln2, H, 1.f, 0.05f, t + 3);
-      w.wgu = dalloc<uint16_t>(2 * I * H);
-      fill(w.wgu, 2 * I * H, 0.f, 0.02f, t + 4);
-      w.wd = dalloc<uint16_t>(H * I);
-      fill(w.wd, H * I, 0.f, 0.02f, t + 5);
+      proj(w.wgu, w.sgu, 2 * I, H, t + 4);
+      proj(w.wd, w.sd, H, I, t + 5);
     }
     hip_check(hipStreamSynchronize(st_), "sync");
   }
@@ -956,17 +1032,17 @@ class Llama {
     size_t stage_bytes = 0;
     try {
       if (head_) {
-        embed_ = dalloc<uint16_t>(V * H);
+        embed_ = walloc16(V * H);
         upload(ck, "model.embed_tokens.weight", embed_, V * H, stage, stage_bytes);
-        norm_ = dalloc<uint16_t>(H);
+        norm_ = walloc16(H);
         upload(ck, "model.norm.weight", norm_, H, stage, stage_bytes);
         const bool own_head = ck.has("lm_head.weight") && !c.tie;
         const char* hn = own_head ? "lm_head.weight" : "model.embed_tokens.weight";
         if (tp_ > 1) {
-          lm_head_ = dalloc<uint16_t>((size_t)lc_.V * H);
+          lm_head_ = walloc16((size_t)lc_.V * H);
           upload_slice(ck, hn, lm_head_, voff_, lc_.V, 0, H, stage, stage_bytes);
         } else if (own_head) {
-          lm_head_ = dalloc<uint16_t>(V * H);
+          lm_head_ = walloc16(V * H);
           upload(ck, hn, lm_head_, V * H, stage, stage_bytes);
         } else {
           lm_head_ = embed_;  // tied embeddings
@@ -976,25 +1052,29 @@ class Llama {
       for (int l : owned_) {
         const std::string p = "model.layers." + std::to_string(l) + ".";
         LayerW& w = layers_[local_[l]];
-        w.ln1 = dalloc<uint16_t>(H);
+        w.ln1 = walloc16(H);
         upload(ck, p + "input_layernorm.weight", w.ln1, H, stage, stage_bytes);
-        w.wqkv = dalloc<uint16_t>((nq + 2 * nk) * H);
-        uint16_t* qkv = reinterpret_cast<uint16_t*>(w.wqkv);
+        // each projection: uploaded as 16-bit rows (its own allocation, or the shared
+        // scratch), then kept or quantised (proj_keep)
+        uint16_t* qkv = proj_stage(nq + 2 * nk, H);
         upload_slice(ck, p + "self_attn.q_proj.weight", qkv, q0, nq, 0, H, stage, stage_bytes);
         upload_slice(ck, p + "self_attn.k_proj.weight", qkv + nq * H, k0, nk, 0, H, stage,
                      stage_bytes);
         upload_slice(ck, p + "self_attn.v_proj.weight", qkv + (nq + nk) * H, k0, nk, 0, H, stage,
                      stage_bytes);
-        w.wo = dalloc<uint16_t>(H * nq);
-        upload_slice(ck, p + "self_attn.o_proj.weight", w.wo, 0, H, q0, nq, stage, stage_bytes);
-        w.ln2 = dalloc<uint16_t>(H);
+        proj_keep(qkv, nq + 2 * nk, H, w.wqkv, w.sqkv);
+        uint16_t* wo = proj_stage(H, nq);
+        upload_slice(ck, p + "self_attn.o_proj.weight", wo, 0, H, q0, nq, stage, stage_bytes);
+        proj_keep(wo, H, nq, w.wo, w.so);
+        w.ln2 = walloc16(H);
         upload(ck, p + "post_attention_layernorm.weight", w.ln2, H, stage, stage_bytes);
-        w.wgu = dalloc<uint16_t>(2 * I * H);
-        uint16_t* gu = reinterpret_cast<uint16_t*>(w.wgu);
+        uint16_t* gu = proj_stage(2 * I, H);
         upload_slice(ck, p + "mlp.gate_proj.weight", gu, i0, I, 0, H, stage, stage_bytes);
         upload_slice(ck, p + "mlp.up_proj.weight", gu + I * H, i0, I, 0, H, stage, stage_bytes);
-        w.wd = dalloc<uint16_t>(H * I);
-        upload_slice(ck, p + "mlp.down_proj.weight", w.wd, 0, H, i0, I, stage, stage_bytes);
+        proj_keep(gu, 2 * I, H, w.wgu, w.sgu);
+        uint16_t* wd = proj_stage(H, I);
+        upload_slice(ck, p + "mlp.down_proj.weight", wd, 0, H, i0, I, stage, stage_bytes);
+        proj_keep(wd, H, I, w.wd, w.sd);
       }
     } catch (...) {
       if (stage) (void)hipFree(stage);
@@ -1042,7 +1122,8 @@ class Llama {
     // MI355X (profiles/r5_attn_oproj_ab.md), kept for the A/B
     {
       const char* e = std::getenv("CAKE_ATTN_OPROJ");
-      if (e && std::string(e) == "1") ao_ = ao_fns();
+      // (reads o_proj as 16-bit rows: off with fp8 weights)
+      if (e && std::string(e) == "1" && wfmt_ == 0) ao_ = ao_fns();
       ao_ok_ = ao_.run != nullptr && ao_.supported(c.nh, c.nkv, c.hd, c.H) != 0;
     }
     // CAKE_ATTN_HEADS=<max keys>[:<waves>]: the head-parallel short-context attention
@@ -1325,8 +1406,17 @@ class Llama {
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
+      // weight_fmt 1: each projection is dequantised into the 16-bit scratch right before
+      // its GEMM (one extra pass over the layer's weights per prefill; stream order keeps
+      // the four uses of the scratch apart)
+      auto w16 = [&](const void* wp, const float* sp, int N, int K) -> const void* {
+        if (wfmt_ == 0) return wp;
+        k_check(cake_dequant_rows_fp8(dt_, wp, sp, N, K, w16_, st_), "dequant_rows_fp8");
+        return w16_;
+      };
       k_check(cake_rmsnorm(dt_, hidden_, w.ln1, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiStore, x16_, c.H, w.wqkv, c.H, qkv_, nqkv, nullptr, 0, T, nqkv, c.H, "gemm qkv");
+      gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr, 0, T,
+           nqkv, c.H, "gemm qkv");
       uint16_t* q = reinterpret_cast<uint16_t*>(qkv_);
       k_check(cake_rope_kv(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
                            inv_freq_, pos0, S_, kc(l), vc(l), st_), "rope_kv");
@@ -1342,15 +1432,18 @@ class Llama {
         gemm(kEpiStore32, att_, nq, w.wo, nq, nullptr, 0, ppart_, c.H, T, c.H, nq, "gemm o");
         dense_allreduce(T);
       } else {
-        gemm(kEpiResid32, att_, nq, w.wo, nq, nullptr, 0, hidden_, c.H, T, c.H, nq, "gemm o");
+        gemm(kEpiResid32, att_, nq, w16(w.wo, w.so, c.H, nq), nq, nullptr, 0, hidden_, c.H, T, c.H,
+             nq, "gemm o");
       }
       k_check(cake_rmsnorm(dt_, hidden_, w.ln2, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiSwiglu, x16_, c.H, w.wgu, c.H, pact_, c.I, nullptr, 0, T, c.I, c.H, "gemm gate|up");
+      gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, 2 * c.I, c.H), c.H, pact_, c.I, nullptr, 0, T,
+           c.I, c.H, "gemm gate|up");
       if (tp_ > 1) {
         gemm(kEpiStore32, pact_, c.I, w.wd, c.I, nullptr, 0, ppart_, c.H, T, c.H, c.I, "gemm down");
         dense_allreduce(T);
       } else {
-        gemm(kEpiResid32, pact_, c.I, w.wd, c.I, nullptr, 0, hidden_, c.H, T, c.H, c.I, "gemm down");
+        gemm(kEpiResid32, pact_, c.I, w16(w.wd, w.sd, c.H, c.I), c.I, nullptr, 0, hidden_, c.H, T,
+             c.H, c.I, "gemm down");
       }
     }
   }
@@ -1475,6 +1568,25 @@ class Llama {
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
+      if (wfmt_ == 1) {  // fp8 projections: the _w8 twins of the four GEMVs (tp_ == 1)
+        const uint8_t* q8 = reinterpret_cast<const uint8_t*>(w.wqkv);
+        k_check(cake_qkv_rope_w8(dt_, resid_, w.ln1, (float)c.eps, q8, q8 + (size_t)nq * c.H,
+                                 q8 + (size_t)(nq + nk) * c.H, w.sqkv, w.sqkv + nq,
+                                 w.sqkv + nq + nk, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
+                                 kc(l), vc(l), S_, st_), "qkv_rope_w8");
+        if (short_step_)  // head-parallel short-context attention
+          k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
+                                         scale(), attn_out_, st_), "attn_heads");
+        else
+          k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
+                                   part_, tickets_, attn_out_, st_), "attn_decode");
+        k_check(cake_gemv_x16_w8(dt_, attn_out_, w.wo, w.so, nq, c.H, resid_, 1, st_), "o_proj_w8");
+        const uint8_t* gu8 = reinterpret_cast<const uint8_t*>(w.wgu);
+        k_check(cake_swiglu_w8(dt_, resid_, w.ln2, (float)c.eps, gu8, gu8 + (size_t)c.I * c.H,
+                               w.sgu, w.sgu + c.I, c.H, c.I, act_, st_), "swiglu_w8");
+        k_check(cake_gemv_x16_w8(dt_, act_, w.wd, w.sd, c.I, c.H, resid_, 1, st_), "down_proj_w8");
+        continue;
+      }
       const uint16_t* wqkv = reinterpret_cast<const uint16_t*>(w.wqkv);
       k_check(cake_qkv_rope(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
                             wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
@@ -2636,6 +2748,7 @@ CAKE_API void* cake_engine_open_tp(const char* model_dir, const CakeEngineOpts* 
                                    const CakeTPOpts* tp, char* err, int32_t errlen) {
   try {
     if (!model_dir || !opts || !tp) throw cake::Error("null argument");
+    if (opts->weight_fmt != 0) throw cake::Error(cake::kNoFp8TP);
     return new Llama(model_dir, *opts, nullptr, nullptr, tp);
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());
@@ -2672,6 +2785,10 @@ CAKE_API int32_t cake_engine_info(void* h, int32_t* o) {
   const int32_t v[8] = {c.V, c.H, c.L, c.nh, c.nkv, c.hd, c.I, m->max_seq()};
   std::memcpy(o, v, sizeof(v));
   return 0;
+}
+
+CAKE_API int64_t cake_engine_weight_bytes(void* h) {
+  return h ? static_cast<Llama*>(h)->weight_bytes() : 0;
 }
 
 CAKE_API int32_t cake_engine_eos(void* h, int32_t* out, int32_t cap) {

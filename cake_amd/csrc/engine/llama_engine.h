@@ -22,7 +22,10 @@ struct CakeEngineOpts {
   int32_t steps_per_graph;  // decode steps per graph replay (greedy only; >= 1)
   int32_t init;             // 0: the checkpoint's safetensors; 1: seeded random-normal
                             // weights of the config.json architecture (benchmarks)
-  int32_t reserved;
+  int32_t weight_fmt;       // 0: projections in the model dtype; 1: FP8 e4m3fn weight-only
+                            // projections (q|k|v, o, gate|up, down: one byte per element
+                            // + one f32 scale per row), quantised on load; the embedding,
+                            // lm_head, norms and KV cache stay 16-bit.  Not with open_tp.
   uint64_t seed;            // init = 1: weight seed
 };
 
@@ -119,6 +122,9 @@ int32_t cake_engine_rank_info(void* engine, int32_t* out4);
 int32_t cake_engine_info(void* engine, int32_t* out8);
 // EOS ids of the config (up to cap); returns the count
 int32_t cake_engine_eos(void* engine, int32_t* out, int32_t cap);
+// bytes of this rank's device weight allocations: embedding, head if untied, norms,
+// projections and (weight_fmt 1) their row scales
+int64_t cake_engine_weight_bytes(void* engine);
 // Prefill `prompt` from position 0, then generate up to max_new tokens (the first comes
 // from the prefill logits), stopping after an EOS id.  Tokens go to out[] (and cb).
 // Returns 0 or an error code (message in err).

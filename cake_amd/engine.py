@@ -23,7 +23,7 @@ TOKEN_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
 
 class EngineOpts(C.Structure):
     _fields_ = [("max_seq", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
-                ("steps_per_graph", C.c_int32), ("init", C.c_int32), ("reserved", C.c_int32),
+                ("steps_per_graph", C.c_int32), ("init", C.c_int32), ("weight_fmt", C.c_int32),
                 ("seed", C.c_uint64)]
 
 
@@ -57,6 +57,9 @@ class EngineStats(C.Structure):
                 ("p99_ms", C.c_float)]
 
 
+# CakeEngineOpts.weight_fmt
+WEIGHT_FORMATS = {"model": 0, "fp8": 1}
+
 _lib = None
 
 
@@ -86,6 +89,8 @@ def lib() -> C.CDLL:
         L.cake_engine_info.restype = I
         L.cake_engine_eos.argtypes = [P, C.POINTER(C.c_int32), I]
         L.cake_engine_eos.restype = I
+        L.cake_engine_weight_bytes.argtypes = [P]
+        L.cake_engine_weight_bytes.restype = C.c_int64
         L.cake_engine_generate.argtypes = [P, C.POINTER(C.c_int32), I, I, C.POINTER(EngineSampling),
                                            C.POINTER(C.c_int32), I, TOKEN_CB, P,
                                            C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
@@ -129,7 +134,8 @@ class NativeLlama:
                  hop_timeout_s: float = 30.0, connect_timeout_s: float = 600.0,
                  tp: bool = False, owners: list[int] | None = None, random_init: bool = False,
                  seed: int = 0, worker_of: list[int] | None = None,
-                 workers: list[str] | None = None, remote_timeout_s: float = 120.0):
+                 workers: list[str] | None = None, remote_timeout_s: float = 120.0,
+                 weights: str = "model"):
         """world > 1: one rank of a layer-sharded pipeline, or with tp=True of a tensor-
         parallel group (rank 0 generates; the others call :meth:`serve`).  Every rank of
         one group must be constructed concurrently.  ``owners`` (pipeline): the rank of
@@ -138,12 +144,20 @@ class NativeLlama:
         draws on the device (benchmarks of a named architecture, no checkpoint).
         ``workers`` / ``worker_of`` (single process): TCP workers ("host:port") and the
         worker index of every layer (-1 = local) — the master's Client
-        (cake-core/src/cake/client.rs:23-133), contiguous runs batched per round trip."""
+        (cake-core/src/cake/client.rs:23-133), contiguous runs batched per round trip.
+        ``weights``: "model" keeps every weight in ``dtype``; "fp8" stores the four
+        per-layer projections (q|k|v, o, gate|up, down) as OCP e4m3fn codes with one f32
+        scale per output row, quantised on load (embedding, lm_head, norms and the KV cache
+        stay in ``dtype``).  Not available with ``tp=True``."""
         if dtype not in ("bf16", "f16"):
             raise ValueError("native engine dtype: bf16 or f16")
+        if weights not in WEIGHT_FORMATS:
+            raise ValueError(f"native engine weights: one of {sorted(WEIGHT_FORMATS)}, "
+                             f"got {weights!r}")
+        self.weights = weights
         opts = EngineOpts(int(max_seq), 0 if dtype == "bf16" else 1, int(device),
-                          max(1, int(steps_per_graph)), 1 if random_init else 0, 0,
-                          int(seed) & 0xFFFFFFFFFFFFFFFF)
+                          max(1, int(steps_per_graph)), 1 if random_init else 0,
+                          WEIGHT_FORMATS[weights], int(seed) & 0xFFFFFFFFFFFFFFFF)
         err = C.create_string_buffer(1024)
         self._h = None
         if world > 1 and tp:
@@ -187,6 +201,11 @@ class NativeLlama:
         eos = (C.c_int32 * 16)()
         n = lib().cake_engine_eos(self._h, eos, 16)
         self.eos_ids = [int(eos[i]) for i in range(min(n, 16))]
+
+    def weight_bytes(self) -> int:
+        """Bytes of this rank's device weight allocations: embedding, head if untied,
+        norms, projections and (``weights="fp8"``) their row scales."""
+        return int(lib().cake_engine_weight_bytes(self._h))
 
     def walk(self) -> str:
         """The token's walk as "rank:first-last" layer runs (comma separated)."""

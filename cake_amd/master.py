@@ -143,6 +143,9 @@ def _load_text(ctx):
         else:
             log.info("text model on the native engine (libcake_engine.so)")
         return NativeLLM.load(ctx)
+    if getattr(ctx, "weight_dtype", "model") == "fp8":
+        from .cli import FP8_NEEDS_NATIVE
+        raise RuntimeError(FP8_NEEDS_NATIVE)
     from .models.llama3.generator import LLamaGenerator
     return LLamaGenerator.load(ctx)
 

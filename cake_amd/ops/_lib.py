@@ -153,3 +153,13 @@ _OPTIONAL = {"cake_mk_gstride", "cake_mk_grid", "cake_mk_supported", "cake_mk_de
 _SIGS["cake_mk_set_stamps"] = [P]
 _SIGS["cake_mk_set_tuning"] = [I, I, I, I]
 _SIGS["cake_attn_debug_drop_partials"] = [I]
+# FP8 e4m3fn weight-only projections (quant_fp8.hip, gemv_w8*.hip)
+_SIGS.update({
+    "cake_quant_rows_fp8": [I, P, I, I, P, P, P],
+    "cake_dequant_rows_fp8": [I, P, P, I, I, P, P],
+    "cake_qkv_rope_w8": [I, P, P, F, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P],
+    "cake_swiglu_w8": [I, P, P, F, P, P, P, P, I, I, P, P],
+    "cake_gemv_x16_w8": [I, P, P, P, I, I, P, I, P],
+    "cake_gemv_w8_set_tuning": [I, I, I, I],
+    "cake_gemv_w8_get_tuning": [I, P],
+})

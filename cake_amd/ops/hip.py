@@ -694,6 +694,99 @@ def set_gemv_tuning(kind: str, U: int = 4, prefetch: int = 0, max_blocks: int = 
           "gemv_set_tuning")
 
 
+# ---------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) weight-only projections: w8 [N, K] uint8 codes + scale [N] f32,
+# W[n, k] = scale[n] * fp8(w8[n, k]); K % 16 == 0 (quant_fp8.hip, gemv_w8*.hip).
+# The oracle is ops/reference.py quant_rows_fp8 / dequant_rows_fp8.
+# ---------------------------------------------------------------------------
+
+def _req_w8(w8, scale, name: str, shape) -> None:
+    _req(w8, name, dtype=torch.uint8, shape=shape)
+    _req(scale, name + " scale", dtype=torch.float32, shape=(shape[0],))
+
+
+def quant_rows_fp8(w16, w8, scale):
+    """16-bit rows [N, K] -> e4m3fn codes w8 [N, K] uint8 and scale [N] f32 = amax / 448."""
+    N, K = w16.shape
+    _dt(w16)
+    _req(w16, "w16")
+    _req_w8(w8, scale, "w8", (N, K))
+    check(kernels().cake_quant_rows_fp8(_dt(w16), _p(w16), N, K, _p(w8), _p(scale), _stream()),
+          "quant_rows_fp8")
+
+
+def dequant_rows_fp8(w8, scale, out16):
+    """out16 [N, K] (bf16 / f16) = scale[n] * fp8(w8[n, k])."""
+    N, K = w8.shape
+    _req_w8(w8, scale, "w8", (N, K))
+    _req(out16, "out16", shape=(N, K))
+    check(kernels().cake_dequant_rows_fp8(_dt(out16), _p(w8), _p(scale), N, K, _p(out16),
+                                          _stream()), "dequant_rows_fp8")
+
+
+def qkv_rope_w8(resid, norm_w, eps, wq, wk, wv, sq, sk, sv, inv_freq, pos, q_out, kcache, vcache):
+    """:func:`qkv_rope` over fp8 weights: wq / wk / wv uint8 codes, sq / sk / sv their f32
+    row scales; the model dtype is the norm weight's and the cache's."""
+    K = resid.numel()
+    nkv, S, hd = kcache.shape
+    nh = wq.shape[0] // hd
+    dt = norm_w.dtype
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_w8(wq, sq, "wq", (nh * hd, K))
+    _req_w8(wk, sk, "wk", (nkv * hd, K))
+    _req_w8(wv, sv, "wv", (nkv * hd, K))
+    _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
+    _req(pos, "pos", dtype=torch.int32, numel=1)
+    _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
+    _req(kcache, "kcache", dtype=dt)
+    _req(vcache, "vcache", dtype=dt, shape=kcache.shape)
+    check(kernels().cake_qkv_rope_w8(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wq),
+                                     _p(wk), _p(wv), _p(sq), _p(sk), _p(sv), K, nh, nkv, hd,
+                                     _p(inv_freq), _p(pos), _p(q_out), _p(kcache), _p(vcache), S,
+                                     _stream()), "qkv_rope_w8")
+
+
+def swiglu_w8(resid, norm_w, eps, wg, wu, sg, su, act):
+    """:func:`swiglu` over fp8 weights (wg / wu uint8 codes, sg / su f32 row scales)."""
+    K = resid.numel()
+    I = wg.shape[0]
+    dt = norm_w.dtype
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_w8(wg, sg, "wg", (I, K))
+    _req_w8(wu, su, "wu", (I, K))
+    _req(act, "act", dtype=dt, numel=I)
+    check(kernels().cake_swiglu_w8(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wg), _p(wu),
+                                   _p(sg), _p(su), K, I, _p(act), _stream()), "swiglu_w8")
+
+
+def gemv_w8(x, w8, scale, out, accumulate: bool):
+    """out (f32) [+]= (scale * fp8(w8)) @ x with a 16-bit x (batch 1)."""
+    N, K = w8.shape
+    _req_w8(w8, scale, "w8", (N, K))
+    _req(x, "x", numel=K)
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_x16_w8(_dt(x), _p(x), _p(w8), _p(scale), K, N, _p(out),
+                                     int(accumulate), _stream()), "gemv_x16_w8")
+
+
+GEMV_W8_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2}
+
+
+def set_gemv_w8_tuning(kind: str, U: int = 4, prefetch: int = 4, max_blocks: int = 1024) -> None:
+    """Launch geometry of one fp8 GEMV kind (gemv_w8.hip): U in {1, 2, 4}, prefetch in
+    {0, 2, 4} chunks per row per lane."""
+    check(kernels().cake_gemv_w8_set_tuning(GEMV_W8_KINDS[kind], int(U), int(prefetch),
+                                            int(max_blocks)), "gemv_w8_set_tuning")
+
+
+def get_gemv_w8_tuning(kind: str) -> tuple[int, int, int]:
+    out = (C.c_int * 3)()
+    check(kernels().cake_gemv_w8_get_tuning(GEMV_W8_KINDS[kind], out), "gemv_w8_get_tuning")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 
 # ---------------------------------------------------------------------------
 # MFMA flash attention + SD normalisation kernels

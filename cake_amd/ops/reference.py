@@ -75,6 +75,27 @@ def silu_mul(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     return gf * torch.sigmoid(gf) * u.float()
 
 
+FP8_E4M3_MAX = 448.0
+
+
+def quant_rows_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """FP8 weight-only storage of a [N, K] matrix (the oracle of quant_fp8.hip).
+
+    scale[n] = amax_n / 448 in f32 (1 for an all-zero row); codes are OCP e4m3fn,
+    ``rne(clamp(float(w) / scale[n], -448, 448))`` — clamped before the conversion, so the
+    NaN code never appears.  Returns (codes uint8 [N, K], scale f32 [N])."""
+    wf = w.float()
+    amax = wf.abs().amax(dim=1)
+    scale = torch.where(amax == 0, torch.ones_like(amax), amax / FP8_E4M3_MAX)
+    v = (wf / scale[:, None]).clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX)
+    return v.to(torch.float8_e4m3fn).view(torch.uint8), scale
+
+
+def dequant_rows_fp8(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """f32 [N, K] = scale[n] * fp8(codes[n, k])."""
+    return codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]
+
+
 def apply_repeat_penalty(logits: torch.Tensor, penalty: float, context: list[int]) -> torch.Tensor:
     """candle_transformers::utils::apply_repeat_penalty semantics (unique tokens)."""
     out = logits.clone()

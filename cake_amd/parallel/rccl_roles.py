@@ -360,7 +360,7 @@ def _native_rank_engine(ctx, rank: int, world: int, tp: bool):
     return NativeLlama(ctx.model_path, max_seq=ctx.max_seq_len, dtype=_dtype_name(ctx.dtype),
                        device=local, rank=rank, world=world, master_addr=addr,
                        hop_bf16=getattr(a, "hop_dtype", "f32") == "bf16", hop_timeout_s=timeout,
-                       tp=tp, owners=owners)
+                       tp=tp, owners=owners, weights=getattr(ctx, "weight_dtype", "model"))
 
 
 def _native_group(ctx) -> bool:
@@ -414,6 +414,9 @@ def run_rccl(ctx) -> None:
     if _native_group(ctx):
         if run_native_rccl(ctx):
             return
+        if getattr(ctx, "weight_dtype", "model") == "fp8":
+            from ..cli import FP8_NEEDS_NATIVE
+            raise RuntimeError(FP8_NEEDS_NATIVE)
         ctx.args.hop = "dist"  # the fallback transport: RCCL p2p / all-reduce
         ctx.args.allreduce = "dist"
     if getattr(ctx.args, "parallel", "pp") == "tp":
