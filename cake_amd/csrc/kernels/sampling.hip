@@ -121,8 +121,12 @@ __device__ __forceinline__ uint32_t philox_u32(uint32_t c0, uint32_t c1, uint32_
 }
 
 __device__ __forceinline__ float gumbel(uint32_t bits) {
-  const float u = (float)(bits >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f;
-  return -__logf(-__logf(u));  // u in (0, 1)
+  // n * 2^-24 + 2^-25 lies in (0, 1), but for n = 2^24 - 1 it is the f32 tie 1 - 2^-25,
+  // which rounds to 1.0 and would give G = +inf (that token wins whatever its logit):
+  // clamp to the largest f32 below 1, so u is in [2^-25, 1 - 2^-24]
+  const float u = fminf((float)(bits >> 8) * 5.9604644775390625e-08f + 2.98023223876953125e-08f,
+                        0x1.fffffep-1f);
+  return -__logf(-__logf(u));
 }
 
 // Per-request sampling parameters read on the device (the API's temperature /

@@ -38,7 +38,7 @@ __device__ __forceinline__ uint4 philox4(uint32_t c0, uint32_t c1, uint32_t k0, 
 }
 
 __device__ __forceinline__ float normal_from(uint32_t a, uint32_t b) {
-  const float u1 = ((float)(a >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1)
+  const float u1 = ((float)(a >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1]: 1.0 for the largest a >> 8 (a zero sample)
   const float u2 = (float)(b >> 8) * 5.9604644775390625e-08f;
   return sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
 }

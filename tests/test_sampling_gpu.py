@@ -6,27 +6,9 @@ import math
 import pytest
 import torch
 
+from _sampling_ref import expected_set as _expected_set  # float64 host rule (shared)
+
 pytestmark = pytest.mark.gpu
-
-
-def _expected_set(logits, T, k, p):
-    """Token set of the host LogitsProcessor (models/sampling.py, candle's
-    TopKThenTopP): top-k, then the top-p cutoff on the top-k tokens' FULL-vocabulary
-    probabilities (not renormalised: a top-k mass below p keeps all k)."""
-    probs = torch.softmax(logits.double() / T, 0)
-    keep = torch.ones_like(probs, dtype=torch.bool)
-    if k:
-        idx = torch.topk(logits, k).indices
-        keep = torch.zeros_like(keep)
-        keep[idx] = True
-    if p is not None and 0 < p < 1:
-        pr = torch.where(keep, probs, torch.zeros_like(probs))
-        order = torch.argsort(pr, descending=True, stable=True)
-        before = torch.cumsum(pr[order], 0) - pr[order]
-        kp = torch.zeros_like(keep)
-        kp[order[before < p]] = True
-        keep &= kp
-    return keep
 
 
 @pytest.mark.parametrize("V,k,p", [(128256, 40, None), (128256, None, 0.9), (128256, 50, 0.8),
