@@ -88,9 +88,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--hop-dtype", choices=["f32", "bf16"], default="f32",
       help="hidden-state payload of an ipc hop (bf16 = the reference's 16-bit transport)")
     a("--max-seq-len", type=int, default=4096)
-    a("--weight-dtype", choices=["model", "fp8"], default="model",
+    a("--weight-dtype", choices=["model", "fp8", "mxfp4"], default="model",
       help="native Llama engine: fp8 = the per-layer projections as e4m3 codes with one "
-           "scale per row, quantised on load (not with --parallel tp); model = --dtype")
+           "scale per row, mxfp4 = as e2m1 codes with one power-of-two scale per 32 "
+           "elements, both quantised on load (not with --parallel tp); model = --dtype")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -118,31 +119,35 @@ def run_parsed(opts: dict) -> int:
     return _run(args)
 
 
-FP8_NEEDS_NATIVE = ("--weight-dtype fp8 is served by the native Llama engine only (a GPU, "
-                    "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
-                    "take the Python path, which has no fp8 weights: refusing rather than "
-                    "running 16-bit")
+def needs_native(fmt: str) -> str:
+    """The refusal of a quantised ``--weight-dtype`` (fp8, mxfp4) on a Python engine path."""
+    return (f"--weight-dtype {fmt} is served by the native Llama engine only (a GPU, "
+            "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
+            f"take the Python path, which has no {fmt} weights: refusing rather than "
+            "running 16-bit")
 
 
-def fp8_refusal(ctx) -> str | None:
-    """Why this context cannot run ``--weight-dtype fp8`` (None: it can, or fp8 is off).
-    Every Python engine path refuses; none silently runs 16-bit."""
-    if getattr(ctx, "weight_dtype", "model") != "fp8":
+def weight_dtype_refusal(ctx) -> str | None:
+    """Why this context cannot run its quantised ``--weight-dtype`` (fp8 or mxfp4; None: it
+    can, or the option is off).  Every Python engine path refuses; none silently runs
+    16-bit."""
+    fmt = getattr(ctx, "weight_dtype", "model")
+    if fmt == "model":
         return None
     a = ctx.args
     if ctx.model_type != "text-model":
-        return "--weight-dtype fp8 applies to the text model only"
+        return f"--weight-dtype {fmt} applies to the text model only"
     from .models.llama3.native_generator import native_eligible
     if not native_eligible(ctx):
-        return FP8_NEEDS_NATIVE
+        return needs_native(fmt)
     if a.transport == "rccl":
         if getattr(a, "parallel", "pp") == "tp":
-            return "--weight-dtype fp8 is not supported with --parallel tp yet"
+            return f"--weight-dtype {fmt} is not supported with --parallel tp yet"
         if getattr(a, "hop", "ipc") != "ipc":
-            return FP8_NEEDS_NATIVE
+            return needs_native(fmt)
     elif a.mode == "worker" or a.transport == "loopback":
         # python -m cake_amd.cli workers are the Python worker (cake-cli hosts the native one)
-        return FP8_NEEDS_NATIVE
+        return needs_native(fmt)
     return None
 
 
@@ -154,7 +159,7 @@ def _run(args) -> int:
     setup_logging(args.log_level)
     from .context import Context
     ctx = Context.from_args(args)
-    why = fp8_refusal(ctx)
+    why = weight_dtype_refusal(ctx)
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

@@ -41,7 +41,7 @@ class Context:
     sampling: SamplingConfig = field(default_factory=SamplingConfig)
     max_seq_len: int = 4096
     no_graph: bool = False
-    weight_dtype: str = "model"  # --weight-dtype: "fp8" = native engine, e4m3 projections
+    weight_dtype: str = "model"  # --weight-dtype: "fp8" / "mxfp4" = native engine only
 
     @classmethod
     def from_args(cls, args) -> "Context":

@@ -105,6 +105,21 @@ int cake_swiglu_w8(int dt, const float* resid, const void* norm_w, float eps, co
                    hipStream_t st);
 int cake_gemv_x16_w8(int dt, const void* x, const void* w, const float* scale, int K, int N,
                      float* out, int accumulate, hipStream_t st);
+// MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
+int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void* e8,
+                          hipStream_t st);
+int cake_dequant_rows_mxfp4(int dt, const void* w4, const void* e8, int N, int K, void* out16,
+                            hipStream_t st);
+int cake_qkv_rope_w4(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
+                     const void* wk, const void* wv, const void* eq, const void* ek,
+                     const void* ev, int K, int nh, int nkv, int hd, const float* inv_freq,
+                     const int* pos, float* q_out, void* kcache, void* vcache, int S,
+                     hipStream_t st);
+int cake_swiglu_w4(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
+                   const void* wu, const void* eg, const void* eu, int K, int I, void* act,
+                   hipStream_t st);
+int cake_gemv_x16_w4(int dt, const void* x, const void* w, const void* e8, int K, int N,
+                     float* out, int accumulate, hipStream_t st);
 int cake_gemv_norm_f32(int dt, const float* resid, const void* norm_w, float eps, const void* w,
                        int K, int N, float* out, hipStream_t st);
 int cake_head_select(int dt, const float* resid, const void* norm_w, float eps, const void* w,
@@ -324,8 +339,9 @@ class Llama {
         const CakeRemoteOpts* remote = nullptr)
       : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), seed_(o.seed) {
     if (dt_ != 0 && dt_ != 1) throw Error("dtype must be 0 (bf16) or 1 (f16)");
-    if (wfmt_ != 0 && wfmt_ != 1)
-      throw Error("weight_fmt must be 0 (model dtype) or 1 (fp8 e4m3 projections)");
+    if (wfmt_ != 0 && wfmt_ != 1 && wfmt_ != 2)
+      throw Error("weight_fmt must be 0 (model dtype), 1 (fp8 e4m3 projections) or 2 (mxfp4 "
+                  "projections)");
     if (wfmt_ != 0 && tp) throw Error(kNoFp8TP);
     if (init_ != 0 && init_ != 1) throw Error("init must be 0 (checkpoint) or 1 (random)");
     if (tp) {
@@ -372,6 +388,8 @@ class Llama {
     }
     if (wfmt_ == 1 && (cfg_.H % 16 || (cfg_.nh * cfg_.hd) % 16 || cfg_.I % 16))
       throw Error("fp8 weights need hidden, attention and intermediate widths divisible by 16");
+    if (wfmt_ == 2 && (cfg_.H % 32 || (cfg_.nh * cfg_.hd) % 32 || cfg_.I % 32))
+      throw Error("mxfp4 weights need hidden, attention and intermediate widths divisible by 32");
     if (layers) {  // a TCP worker: the topology node's layers, no embedding / head
       owned_ = *layers;
       std::sort(owned_.begin(), owned_.end());
@@ -425,7 +443,9 @@ class Llama {
     std::fprintf(stderr, "cake engine: weights %s, %lld bytes on device (rank %d, %d layers)\n",
                  wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
                                         : "fp8 e4m3 projections (f16 rest)")
-                            : (dt_ == 0 ? "bf16" : "f16"),
+                 : wfmt_ == 2 ? (dt_ == 0 ? "mxfp4 projections (bf16 rest)"
+                                          : "mxfp4 projections (f16 rest)")
+                              : (dt_ == 0 ? "bf16" : "f16"),
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
@@ -735,10 +755,12 @@ class Llama {
 
  private:
   // weight_fmt 1: wqkv / wo / wgu / wd hold e4m3 codes, s* their f32 row scales (packed as
-  // the rows are: q|k|v, gate|up)
+  // the rows are: q|k|v, gate|up).  weight_fmt 2: they hold packed e2m1 codes [N, K/2], e*
+  // their e8m0 block-scale bytes [N, K/32] (packed the same way).
   struct LayerW {
     void *ln1, *wqkv, *wo, *ln2, *wgu, *wd;
     float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
+    uint8_t *eqkv = nullptr, *eo = nullptr, *egu = nullptr, *ed = nullptr;
   };
   struct Mode {
     bool fused = true;  // greedy with the fused head_select tail
@@ -756,7 +778,7 @@ class Llama {
   int dt_, dev_, init_ = 0;
   int wfmt_ = 0;               // CakeEngineOpts.weight_fmt
   int64_t weight_bytes_ = 0;   // device weight allocations of this rank
-  // weight_fmt 1: 16-bit scratch for the largest projection — the loader fills it before
+  // weight_fmt 1, 2: 16-bit scratch for the largest projection — the loader fills it before
   // each quantise (the 16-bit copy is never kept), prefill dequantises into it before
   // each GEMM
   uint16_t* w16_ = nullptr;
@@ -942,7 +964,7 @@ class Llama {
     return dalloc<uint16_t>(n);
   }
   // where the loader writes the 16-bit rows of a projection [N, K]: the tensor's own
-  // allocation, or (weight_fmt 1) the shared scratch, sized for the largest projection
+  // allocation, or (weight_fmt 1, 2) the shared scratch, sized for the largest projection
   uint16_t* proj_stage(size_t N, size_t K) {
     if (wfmt_ == 0) return walloc16(N * K);
     if (!w16_) {
@@ -953,10 +975,20 @@ class Llama {
     return w16_;
   }
   // keep what proj_stage's buffer now holds: as it is, or quantised into its own codes +
-  // row scales (quant_fp8.hip); the scratch is free again on return
-  void proj_keep(uint16_t* staged, size_t N, size_t K, void*& w, float*& sc) {
+  // row scales (quant_fp8.hip) or codes + block-scale bytes (quant_mxfp4.hip); the scratch
+  // is free again on return
+  void proj_keep(uint16_t* staged, size_t N, size_t K, void*& w, float*& sc, uint8_t*& e8) {
     if (wfmt_ == 0) {
       w = staged;
+      return;
+    }
+    if (wfmt_ == 2) {
+      uint8_t* w4 = dalloc<uint8_t>(N * K / 2);
+      e8 = dalloc<uint8_t>(N * K / 32);
+      weight_bytes_ += (int64_t)(N * K / 2 + N * K / 32);
+      k_check(cake_quant_rows_mxfp4(dt_, staged, (int)N, (int)K, w4, e8, st_), "quant_rows_mxfp4");
+      hip_check(hipStreamSynchronize(st_), "sync");
+      w = w4;
       return;
     }
     uint8_t* w8 = dalloc<uint8_t>(N * K);
@@ -1000,19 +1032,19 @@ class Llama {
       LayerW& w = layers_[local_[l]];
       const uint64_t t = 16 + 16 * (uint64_t)l;
       // a projection [N, K]: drawn as 16-bit rows, kept or quantised (proj_keep)
-      auto proj = [&](void*& wp, float*& sp, size_t N, size_t K, uint64_t tag) {
+      auto proj = [&](void*& wp, float*& sp, uint8_t*& ep, size_t N, size_t K, uint64_t tag) {
         uint16_t* p = proj_stage(N, K);
         fill(p, N * K, 0.f, 0.02f, tag);
-        proj_keep(p, N, K, wp, sp);
+        proj_keep(p, N, K, wp, sp, ep);
       };
       w.ln1 = walloc16(H);
       fill(w.ln1, H, 1.f, 0.05f, t);
-      proj(w.wqkv, w.sqkv, nq + 2 * nk, H, t + 1);
-      proj(w.wo, w.so, H, nq, t + 2);
+      proj(w.wqkv, w.sqkv, w.eqkv, nq + 2 * nk, H, t + 1);
+      proj(w.wo, w.so, w.eo, H, nq, t + 2);
       w.ln2 = walloc16(H);
       fill(w.ln2, H, 1.f, 0.05f, t + 3);
-      proj(w.wgu, w.sgu, 2 * I, H, t + 4);
-      proj(w.wd, w.sd, H, I, t + 5);
+      proj(w.wgu, w.sgu, w.egu, 2 * I, H, t + 4);
+      proj(w.wd, w.sd, w.ed, H, I, t + 5);
     }
     hip_check(hipStreamSynchronize(st_), "sync");
   }
@@ -1062,19 +1094,19 @@ class Llama {
                      stage_bytes);
         upload_slice(ck, p + "self_attn.v_proj.weight", qkv + (nq + nk) * H, k0, nk, 0, H, stage,
                      stage_bytes);
-        proj_keep(qkv, nq + 2 * nk, H, w.wqkv, w.sqkv);
+        proj_keep(qkv, nq + 2 * nk, H, w.wqkv, w.sqkv, w.eqkv);
         uint16_t* wo = proj_stage(H, nq);
         upload_slice(ck, p + "self_attn.o_proj.weight", wo, 0, H, q0, nq, stage, stage_bytes);
-        proj_keep(wo, H, nq, w.wo, w.so);
+        proj_keep(wo, H, nq, w.wo, w.so, w.eo);
         w.ln2 = walloc16(H);
         upload(ck, p + "post_attention_layernorm.weight", w.ln2, H, stage, stage_bytes);
         uint16_t* gu = proj_stage(2 * I, H);
         upload_slice(ck, p + "mlp.gate_proj.weight", gu, i0, I, 0, H, stage, stage_bytes);
         upload_slice(ck, p + "mlp.up_proj.weight", gu + I * H, i0, I, 0, H, stage, stage_bytes);
-        proj_keep(gu, 2 * I, H, w.wgu, w.sgu);
+        proj_keep(gu, 2 * I, H, w.wgu, w.sgu, w.egu);
         uint16_t* wd = proj_stage(H, I);
         upload_slice(ck, p + "mlp.down_proj.weight", wd, 0, H, i0, I, stage, stage_bytes);
-        proj_keep(wd, H, I, w.wd, w.sd);
+        proj_keep(wd, H, I, w.wd, w.sd, w.ed);
       }
     } catch (...) {
       if (stage) (void)hipFree(stage);
@@ -1122,7 +1154,7 @@ class Llama {
     // MI355X (profiles/r5_attn_oproj_ab.md), kept for the A/B
     {
       const char* e = std::getenv("CAKE_ATTN_OPROJ");
-      // (reads o_proj as 16-bit rows: off with fp8 weights)
+      // (reads o_proj as 16-bit rows: off with fp8 and mxfp4 weights)
       if (e && std::string(e) == "1" && wfmt_ == 0) ao_ = ao_fns();
       ao_ok_ = ao_.run != nullptr && ao_.supported(c.nh, c.nkv, c.hd, c.H) != 0;
     }
@@ -1406,17 +1438,21 @@ class Llama {
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
-      // weight_fmt 1: each projection is dequantised into the 16-bit scratch right before
+      // weight_fmt 1, 2: each projection is dequantised into the 16-bit scratch right before
       // its GEMM (one extra pass over the layer's weights per prefill; stream order keeps
       // the four uses of the scratch apart)
-      auto w16 = [&](const void* wp, const float* sp, int N, int K) -> const void* {
+      auto w16 = [&](const void* wp, const float* sp, const uint8_t* ep, int N,
+                     int K) -> const void* {
         if (wfmt_ == 0) return wp;
-        k_check(cake_dequant_rows_fp8(dt_, wp, sp, N, K, w16_, st_), "dequant_rows_fp8");
+        if (wfmt_ == 2)
+          k_check(cake_dequant_rows_mxfp4(dt_, wp, ep, N, K, w16_, st_), "dequant_rows_mxfp4");
+        else
+          k_check(cake_dequant_rows_fp8(dt_, wp, sp, N, K, w16_, st_), "dequant_rows_fp8");
         return w16_;
       };
       k_check(cake_rmsnorm(dt_, hidden_, w.ln1, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr, 0, T,
-           nqkv, c.H, "gemm qkv");
+      gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, w.eqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr,
+           0, T, nqkv, c.H, "gemm qkv");
       uint16_t* q = reinterpret_cast<uint16_t*>(qkv_);
       k_check(cake_rope_kv(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
                            inv_freq_, pos0, S_, kc(l), vc(l), st_), "rope_kv");
@@ -1432,18 +1468,18 @@ class Llama {
         gemm(kEpiStore32, att_, nq, w.wo, nq, nullptr, 0, ppart_, c.H, T, c.H, nq, "gemm o");
         dense_allreduce(T);
       } else {
-        gemm(kEpiResid32, att_, nq, w16(w.wo, w.so, c.H, nq), nq, nullptr, 0, hidden_, c.H, T, c.H,
-             nq, "gemm o");
+        gemm(kEpiResid32, att_, nq, w16(w.wo, w.so, w.eo, c.H, nq), nq, nullptr, 0, hidden_, c.H, T,
+             c.H, nq, "gemm o");
       }
       k_check(cake_rmsnorm(dt_, hidden_, w.ln2, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, 2 * c.I, c.H), c.H, pact_, c.I, nullptr, 0, T,
-           c.I, c.H, "gemm gate|up");
+      gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, w.egu, 2 * c.I, c.H), c.H, pact_, c.I, nullptr,
+           0, T, c.I, c.H, "gemm gate|up");
       if (tp_ > 1) {
         gemm(kEpiStore32, pact_, c.I, w.wd, c.I, nullptr, 0, ppart_, c.H, T, c.H, c.I, "gemm down");
         dense_allreduce(T);
       } else {
-        gemm(kEpiResid32, pact_, c.I, w16(w.wd, w.sd, c.H, c.I), c.I, nullptr, 0, hidden_, c.H, T,
-             c.H, c.I, "gemm down");
+        gemm(kEpiResid32, pact_, c.I, w16(w.wd, w.sd, w.ed, c.H, c.I), c.I, nullptr, 0, hidden_, c.H,
+             T, c.H, c.I, "gemm down");
       }
     }
   }
@@ -1568,6 +1604,26 @@ class Llama {
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
+      if (wfmt_ == 2) {  // mxfp4 projections: the _w4 twins of the four GEMVs (tp_ == 1)
+        const uint8_t* q4 = reinterpret_cast<const uint8_t*>(w.wqkv);
+        const size_t rb = (size_t)c.H / 2, re = (size_t)c.H / 32;  // bytes per q|k|v row
+        k_check(cake_qkv_rope_w4(dt_, resid_, w.ln1, (float)c.eps, q4, q4 + (size_t)nq * rb,
+                                 q4 + (size_t)(nq + nk) * rb, w.eqkv, w.eqkv + (size_t)nq * re,
+                                 w.eqkv + (size_t)(nq + nk) * re, c.H, c.nh, c.nkv, c.hd,
+                                 inv_freq_, pos_, q_, kc(l), vc(l), S_, st_), "qkv_rope_w4");
+        if (short_step_)  // head-parallel short-context attention
+          k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
+                                         scale(), attn_out_, st_), "attn_heads");
+        else
+          k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
+                                   part_, tickets_, attn_out_, st_), "attn_decode");
+        k_check(cake_gemv_x16_w4(dt_, attn_out_, w.wo, w.eo, nq, c.H, resid_, 1, st_), "o_proj_w4");
+        const uint8_t* gu4 = reinterpret_cast<const uint8_t*>(w.wgu);
+        k_check(cake_swiglu_w4(dt_, resid_, w.ln2, (float)c.eps, gu4, gu4 + (size_t)c.I * rb,
+                               w.egu, w.egu + (size_t)c.I * re, c.H, c.I, act_, st_), "swiglu_w4");
+        k_check(cake_gemv_x16_w4(dt_, act_, w.wd, w.ed, c.I, c.H, resid_, 1, st_), "down_proj_w4");
+        continue;
+      }
       if (wfmt_ == 1) {  // fp8 projections: the _w8 twins of the four GEMVs (tp_ == 1)
         const uint8_t* q8 = reinterpret_cast<const uint8_t*>(w.wqkv);
         k_check(cake_qkv_rope_w8(dt_, resid_, w.ln1, (float)c.eps, q8, q8 + (size_t)nq * c.H,

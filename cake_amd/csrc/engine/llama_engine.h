@@ -25,7 +25,10 @@ struct CakeEngineOpts {
   int32_t weight_fmt;       // 0: projections in the model dtype; 1: FP8 e4m3fn weight-only
                             // projections (q|k|v, o, gate|up, down: one byte per element
                             // + one f32 scale per row), quantised on load; the embedding,
-                            // lm_head, norms and KV cache stay 16-bit.  Not with open_tp.
+                            // lm_head, norms and KV cache stay 16-bit; 2: OCP MXFP4
+                            // weight-only projections (the same four: two e2m1 codes per
+                            // byte + one e8m0 scale byte per 32 elements of a row; widths
+                            // divisible by 32), quantised on load.  1, 2: not with open_tp.
   uint64_t seed;            // init = 1: weight seed
 };
 
@@ -123,7 +126,7 @@ int32_t cake_engine_info(void* engine, int32_t* out8);
 // EOS ids of the config (up to cap); returns the count
 int32_t cake_engine_eos(void* engine, int32_t* out, int32_t cap);
 // bytes of this rank's device weight allocations: embedding, head if untied, norms,
-// projections and (weight_fmt 1) their row scales
+// projections and their scales (weight_fmt 1: f32 per row; 2: one byte per 32 elements)
 int64_t cake_engine_weight_bytes(void* engine);
 // Prefill `prompt` from position 0, then generate up to max_new tokens (the first comes
 // from the prefill logits), stopping after an EOS id.  Tokens go to out[] (and cb).

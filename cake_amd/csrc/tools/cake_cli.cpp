@@ -101,9 +101,10 @@ const Flag kFlags[] = {
      "rccl pp: device-side graph hops (ipc) or host-issued RCCL p2p (dist)"},
     {"--hop-dtype", "hop_dtype", PyArg::kStr, "f32", "f32|bf16", false, "ipc hop payload"},
     {"--max-seq-len", "max_seq_len", PyArg::kInt, "4096", nullptr, false, "KV cache length"},
-    {"--weight-dtype", "weight_dtype", PyArg::kStr, "model", "model|fp8", false,
-     "native Llama engine: fp8 = e4m3 per-layer projections with one scale per row, quantised "
-     "on load (not with --parallel tp); model = --dtype"},
+    {"--weight-dtype", "weight_dtype", PyArg::kStr, "model", "model|fp8|mxfp4", false,
+     "native Llama engine: fp8 = e4m3 per-layer projections with one scale per row, mxfp4 = "
+     "e2m1 projections with one power-of-two scale per 32 elements, both quantised on load "
+     "(not with --parallel tp); model = --dtype"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -186,6 +187,9 @@ int env_int(const char* k, int def) {
   const char* v = std::getenv(k);
   return v ? std::atoi(v) : def;
 }
+
+// --weight-dtype -> CakeEngineOpts.weight_fmt (the choices are checked by the parser)
+int32_t weight_fmt_of(const std::string& v) { return v == "fp8" ? 1 : (v == "mxfp4" ? 2 : 0); }
 
 struct StreamCtx {
   std::string model;
@@ -292,7 +296,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     };
     CakeEngineOpts eo{(int32_t)num("max_seq_len", 4096), o["dtype"].value == "bf16" ? 0 : 1,
                       env_int("LOCAL_RANK", rank), 1};
-    eo.weight_fmt = o["weight_dtype"].value == "fp8" ? 1 : 0;
+    eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
     CakePipeOpts po{rank, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
                     owners.empty() ? nullptr : owners.data(), (int32_t)owners.size()};
     CakeTPOpts to{rank, world, ctl.c_str(), 60.0, 600.0};
@@ -329,7 +333,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   eo.dtype = o["dtype"].value == "bf16" ? 0 : 1;  // reference default: f16
   eo.device = pipe ? env_int("LOCAL_RANK", 0) : (int32_t)num("device", 0);
   eo.steps_per_graph = 1;
-  eo.weight_fmt = o["weight_dtype"].value == "fp8" ? 1 : 0;
+  eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
   char err[1024] = {0};
   const auto t0 = std::chrono::steady_clock::now();
   CakePipeOpts po{0, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
@@ -442,7 +446,7 @@ int run_native_worker(cake::PyArgs& o, const cake::TopoNode& node) {
   w.device = o["device"].kind == PyArg::kNone ? 0 : std::atoi(o["device"].value.c_str());
   w.max_seq = o["max_seq_len"].kind == PyArg::kNone ? 4096 : std::atoi(o["max_seq_len"].value.c_str());
   w.bf16 = o["dtype"].value == "bf16";
-  w.fp8 = o["weight_dtype"].value == "fp8";
+  w.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
   return cake::run_native_worker(w, node);
 }
 

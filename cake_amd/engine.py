@@ -58,7 +58,7 @@ class EngineStats(C.Structure):
 
 
 # CakeEngineOpts.weight_fmt
-WEIGHT_FORMATS = {"model": 0, "fp8": 1}
+WEIGHT_FORMATS = {"model": 0, "fp8": 1, "mxfp4": 2}
 
 _lib = None
 
@@ -148,7 +148,9 @@ class NativeLlama:
         ``weights``: "model" keeps every weight in ``dtype``; "fp8" stores the four
         per-layer projections (q|k|v, o, gate|up, down) as OCP e4m3fn codes with one f32
         scale per output row, quantised on load (embedding, lm_head, norms and the KV cache
-        stay in ``dtype``).  Not available with ``tp=True``."""
+        stay in ``dtype``); "mxfp4" stores them as OCP MXFP4, two e2m1 codes per byte with one
+        power-of-two scale byte per 32 elements of a row (widths divisible by 32), also
+        quantised on load.  Neither is available with ``tp=True``."""
         if dtype not in ("bf16", "f16"):
             raise ValueError("native engine dtype: bf16 or f16")
         if weights not in WEIGHT_FORMATS:
@@ -204,7 +206,8 @@ class NativeLlama:
 
     def weight_bytes(self) -> int:
         """Bytes of this rank's device weight allocations: embedding, head if untied,
-        norms, projections and (``weights="fp8"``) their row scales."""
+        norms, projections and their scales (``weights="fp8"``: one f32 per row;
+        ``"mxfp4"``: one byte per 32 elements)."""
         return int(lib().cake_engine_weight_bytes(self._h))
 
     def walk(self) -> str:

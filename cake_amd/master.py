@@ -143,9 +143,9 @@ def _load_text(ctx):
         else:
             log.info("text model on the native engine (libcake_engine.so)")
         return NativeLLM.load(ctx)
-    if getattr(ctx, "weight_dtype", "model") == "fp8":
-        from .cli import FP8_NEEDS_NATIVE
-        raise RuntimeError(FP8_NEEDS_NATIVE)
+    if getattr(ctx, "weight_dtype", "model") != "model":
+        from .cli import needs_native
+        raise RuntimeError(needs_native(ctx.weight_dtype))
     from .models.llama3.generator import LLamaGenerator
     return LLamaGenerator.load(ctx)
 

@@ -163,3 +163,13 @@ _SIGS.update({
     "cake_gemv_w8_set_tuning": [I, I, I, I],
     "cake_gemv_w8_get_tuning": [I, P],
 })
+# MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
+_SIGS.update({
+    "cake_quant_rows_mxfp4": [I, P, I, I, P, P, P],
+    "cake_dequant_rows_mxfp4": [I, P, P, I, I, P, P],
+    "cake_qkv_rope_w4": [I, P, P, F, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P],
+    "cake_swiglu_w4": [I, P, P, F, P, P, P, P, I, I, P, P],
+    "cake_gemv_x16_w4": [I, P, P, P, I, I, P, I, P],
+    "cake_gemv_w4_set_tuning": [I, I, I, I],
+    "cake_gemv_w4_get_tuning": [I, P],
+})

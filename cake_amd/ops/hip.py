@@ -787,6 +787,103 @@ def get_gemv_w8_tuning(kind: str) -> tuple[int, int, int]:
     return int(out[0]), int(out[1]), int(out[2])
 
 
+# ---------------------------------------------------------------------------
+# MXFP4 weight-only projections: w4 [N, K/2] uint8 (two e2m1 codes per byte, k even in the
+# low nibble) + e8 [N, K/32] uint8 e8m0 block scales,
+# W[n, k] = 2^(e8[n, k/32] - 127) * e2m1(code); K % 32 == 0 (quant_mxfp4.hip, gemv_w4*.hip).
+# The oracle is ops/reference.py quant_rows_mxfp4 / dequant_rows_mxfp4.
+# ---------------------------------------------------------------------------
+
+def _req_w4(w4, e8, name: str, shape) -> None:
+    N, K = shape
+    _req(w4, name, dtype=torch.uint8, shape=(N, K // 2))
+    _req(e8, name + " scales", dtype=torch.uint8, shape=(N, K // 32))
+
+
+def quant_rows_mxfp4(w16, w4, e8):
+    """16-bit rows [N, K] -> packed e2m1 codes w4 [N, K/2] uint8 and block scales e8
+    [N, K/32] uint8."""
+    N, K = w16.shape
+    _dt(w16)
+    _req(w16, "w16")
+    _req_w4(w4, e8, "w4", (N, K))
+    check(kernels().cake_quant_rows_mxfp4(_dt(w16), _p(w16), N, K, _p(w4), _p(e8), _stream()),
+          "quant_rows_mxfp4")
+
+
+def dequant_rows_mxfp4(w4, e8, out16):
+    """out16 [N, K] (bf16 / f16) = 2^(e8[n, k/32] - 127) * e2m1(code[n, k])."""
+    N, K = out16.shape
+    _req_w4(w4, e8, "w4", (N, K))
+    _req(out16, "out16", shape=(N, K))
+    check(kernels().cake_dequant_rows_mxfp4(_dt(out16), _p(w4), _p(e8), N, K, _p(out16),
+                                            _stream()), "dequant_rows_mxfp4")
+
+
+def qkv_rope_w4(resid, norm_w, eps, wq, wk, wv, eq, ek, ev, inv_freq, pos, q_out, kcache, vcache):
+    """:func:`qkv_rope` over MXFP4 weights: wq / wk / wv packed codes, eq / ek / ev their
+    block-scale bytes; the model dtype is the norm weight's and the cache's."""
+    K = resid.numel()
+    nkv, S, hd = kcache.shape
+    nh = wq.shape[0] // hd
+    dt = norm_w.dtype
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_w4(wq, eq, "wq", (nh * hd, K))
+    _req_w4(wk, ek, "wk", (nkv * hd, K))
+    _req_w4(wv, ev, "wv", (nkv * hd, K))
+    _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
+    _req(pos, "pos", dtype=torch.int32, numel=1)
+    _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
+    _req(kcache, "kcache", dtype=dt)
+    _req(vcache, "vcache", dtype=dt, shape=kcache.shape)
+    check(kernels().cake_qkv_rope_w4(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wq),
+                                     _p(wk), _p(wv), _p(eq), _p(ek), _p(ev), K, nh, nkv, hd,
+                                     _p(inv_freq), _p(pos), _p(q_out), _p(kcache), _p(vcache), S,
+                                     _stream()), "qkv_rope_w4")
+
+
+def swiglu_w4(resid, norm_w, eps, wg, wu, eg, eu, act):
+    """:func:`swiglu` over MXFP4 weights (wg / wu packed codes, eg / eu block-scale bytes)."""
+    K = resid.numel()
+    I = wg.shape[0]
+    dt = norm_w.dtype
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_w4(wg, eg, "wg", (I, K))
+    _req_w4(wu, eu, "wu", (I, K))
+    _req(act, "act", dtype=dt, numel=I)
+    check(kernels().cake_swiglu_w4(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wg), _p(wu),
+                                   _p(eg), _p(eu), K, I, _p(act), _stream()), "swiglu_w4")
+
+
+def gemv_w4(x, w4, e8, out, accumulate: bool):
+    """out (f32) [+]= dequant(w4, e8) @ x with a 16-bit x (batch 1)."""
+    N = w4.shape[0]
+    K = x.numel()
+    _req_w4(w4, e8, "w4", (N, K))
+    _req(x, "x", numel=K)
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_x16_w4(_dt(x), _p(x), _p(w4), _p(e8), K, N, _p(out),
+                                     int(accumulate), _stream()), "gemv_x16_w4")
+
+
+GEMV_W4_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2}
+
+
+def set_gemv_w4_tuning(kind: str, U: int = 2, prefetch: int = 4, max_blocks: int = 1024) -> None:
+    """Launch geometry of one MXFP4 GEMV kind (gemv_w4.hip): U in {1, 2, 4}, prefetch in
+    {0, 2, 4} chunks per row per lane (run as the deepest depth the row fills)."""
+    check(kernels().cake_gemv_w4_set_tuning(GEMV_W4_KINDS[kind], int(U), int(prefetch),
+                                            int(max_blocks)), "gemv_w4_set_tuning")
+
+
+def get_gemv_w4_tuning(kind: str) -> tuple[int, int, int]:
+    out = (C.c_int * 3)()
+    check(kernels().cake_gemv_w4_get_tuning(GEMV_W4_KINDS[kind], out), "gemv_w4_get_tuning")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
 
 # ---------------------------------------------------------------------------
 # MFMA flash attention + SD normalisation kernels

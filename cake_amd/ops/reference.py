@@ -96,6 +96,50 @@ def dequant_rows_fp8(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]
 
 
+MXFP4_BLOCK = 32
+# e2m1 magnitudes by code (s e e m: the sign is bit 3) and the midpoints between them
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+E2M1_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)
+
+
+def quant_rows_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """OCP MXFP4 weight-only storage of a [N, K] matrix, K % 32 == 0 (the oracle of
+    quant_mxfp4.hip): e2m1 elements with one e8m0 power-of-two scale per 32 consecutive k.
+
+    Scale: ``e = clamp(floor(log2(amax_block)) - 2, -126, 127)`` stored as the byte
+    ``e + 127`` (127 for an all-zero block; never 0xFF).  Element: ``v = w / 2^e`` (exact),
+    ``|v|`` saturated to 6 and rounded to the nearest of {0, .5, 1, 1.5, 2, 3, 4, 6}, ties
+    to the even code; bit 3 is the sign bit of ``w`` (a small negative may become -0).
+    Element 2i sits in the low nibble of byte i, 2i+1 in the high nibble.
+    Returns (codes uint8 [N, K/2], e8 uint8 [N, K/32])."""
+    N, K = w.shape
+    if K < MXFP4_BLOCK or K % MXFP4_BLOCK:
+        raise ValueError(f"mxfp4 rows need K % {MXFP4_BLOCK} == 0, got {K}")
+    wf = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    fl = torch.frexp(amax)[1] - 1  # floor(log2(amax)), exact (any value where amax == 0)
+    e = torch.where(amax == 0, torch.zeros_like(fl), (fl - 2).clamp(-126, 127))
+    a = torch.ldexp(wf.abs(), -e[:, :, None])
+    mid = torch.tensor(E2M1_MIDPOINTS, dtype=torch.float32, device=w.device)
+    mag = torch.bucketize(a, mid)  # midpoints strictly below |v|: a tie stays on the lower code
+    # ... and moves up where the upper code is the even one
+    mag = mag + ((a == 0.75) | (a == 1.75) | (a == 3.5)).to(mag.dtype)
+    code = (mag | (torch.signbit(wf).to(mag.dtype) << 3)).reshape(N, K // 2, 2)
+    packed = (code[:, :, 0] | (code[:, :, 1] << 4)).to(torch.uint8)
+    return packed, (e + 127).to(torch.uint8)
+
+
+def dequant_rows_mxfp4(codes: torch.Tensor, e8: torch.Tensor) -> torch.Tensor:
+    """f32 [N, K] = 2^(e8[n, k / 32] - 127) * e2m1(code[n, k])."""
+    N, K2 = codes.shape
+    c = codes.to(torch.int64)
+    nib = torch.stack((c & 15, c >> 4), dim=2).reshape(N, 2 * K2)
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32,
+                       device=codes.device)
+    e = e8.to(torch.int32) - 127
+    return torch.ldexp(lut[nib].reshape(N, -1, MXFP4_BLOCK), e[:, :, None]).reshape(N, 2 * K2)
+
+
 def apply_repeat_penalty(logits: torch.Tensor, penalty: float, context: list[int]) -> torch.Tensor:
     """candle_transformers::utils::apply_repeat_penalty semantics (unique tokens)."""
     out = logits.clone()

@@ -414,9 +414,9 @@ def run_rccl(ctx) -> None:
     if _native_group(ctx):
         if run_native_rccl(ctx):
             return
-        if getattr(ctx, "weight_dtype", "model") == "fp8":
-            from ..cli import FP8_NEEDS_NATIVE
-            raise RuntimeError(FP8_NEEDS_NATIVE)
+        if getattr(ctx, "weight_dtype", "model") != "model":
+            from ..cli import needs_native
+            raise RuntimeError(needs_native(ctx.weight_dtype))
         ctx.args.hop = "dist"  # the fallback transport: RCCL p2p / all-reduce
         ctx.args.allreduce = "dist"
     if getattr(ctx.args, "parallel", "pp") == "tp":
