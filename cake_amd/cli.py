@@ -92,6 +92,10 @@ def build_parser() -> argparse.ArgumentParser:
       help="native Llama engine: fp8 = the per-layer projections as e4m3 codes with one "
            "scale per row, mxfp4 = as e2m1 codes with one power-of-two scale per 32 "
            "elements, both quantised on load (not with --parallel tp); model = --dtype")
+    a("--head-dtype", choices=["model", "fp8", "mxfp4"], default="model",
+      help="native Llama engine: the lm_head as fp8 (e4m3 codes, one scale per vocabulary "
+           "row) or mxfp4, quantised on load, chosen independently of --weight-dtype (not "
+           "with --parallel tp; workers hold no head and ignore it); model = --dtype")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -119,36 +123,48 @@ def run_parsed(opts: dict) -> int:
     return _run(args)
 
 
-def needs_native(fmt: str) -> str:
-    """The refusal of a quantised ``--weight-dtype`` (fp8, mxfp4) on a Python engine path."""
-    return (f"--weight-dtype {fmt} is served by the native Llama engine only (a GPU, "
+def needs_native(fmt: str, flag: str = "--weight-dtype") -> str:
+    """The refusal of a quantised ``--weight-dtype`` / ``--head-dtype`` (fp8, mxfp4) on a
+    Python engine path."""
+    return (f"{flag} {fmt} is served by the native Llama engine only (a GPU, "
             "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
             f"take the Python path, which has no {fmt} weights: refusing rather than "
             "running 16-bit")
+
+
+def _quant_refusal(ctx, flag: str, fmt: str) -> str | None:
+    if fmt == "model":
+        return None
+    a = ctx.args
+    if ctx.model_type != "text-model":
+        return f"{flag} {fmt} applies to the text model only"
+    from .models.llama3.native_generator import native_eligible
+    if not native_eligible(ctx):
+        return needs_native(fmt, flag)
+    if a.transport == "rccl":
+        if getattr(a, "parallel", "pp") == "tp":
+            return f"{flag} {fmt} is not supported with --parallel tp yet"
+        if getattr(a, "hop", "ipc") != "ipc":
+            return needs_native(fmt, flag)
+    elif a.mode == "worker" or a.transport == "loopback":
+        # python -m cake_amd.cli workers are the Python worker (cake-cli hosts the native one)
+        return needs_native(fmt, flag)
+    return None
 
 
 def weight_dtype_refusal(ctx) -> str | None:
     """Why this context cannot run its quantised ``--weight-dtype`` (fp8 or mxfp4; None: it
     can, or the option is off).  Every Python engine path refuses; none silently runs
     16-bit."""
-    fmt = getattr(ctx, "weight_dtype", "model")
-    if fmt == "model":
+    return _quant_refusal(ctx, "--weight-dtype", getattr(ctx, "weight_dtype", "model"))
+
+
+def head_dtype_refusal(ctx) -> str | None:
+    """The same for ``--head-dtype``, in the same wording.  A worker holds no head, so
+    ``--mode worker`` accepts the option and ignores it."""
+    if getattr(ctx.args, "mode", "master") == "worker" and ctx.model_type == "text-model":
         return None
-    a = ctx.args
-    if ctx.model_type != "text-model":
-        return f"--weight-dtype {fmt} applies to the text model only"
-    from .models.llama3.native_generator import native_eligible
-    if not native_eligible(ctx):
-        return needs_native(fmt)
-    if a.transport == "rccl":
-        if getattr(a, "parallel", "pp") == "tp":
-            return f"--weight-dtype {fmt} is not supported with --parallel tp yet"
-        if getattr(a, "hop", "ipc") != "ipc":
-            return needs_native(fmt)
-    elif a.mode == "worker" or a.transport == "loopback":
-        # python -m cake_amd.cli workers are the Python worker (cake-cli hosts the native one)
-        return needs_native(fmt)
-    return None
+    return _quant_refusal(ctx, "--head-dtype", getattr(ctx, "head_dtype", "model"))
 
 
 def main(argv: list[str] | None = None) -> int:
@@ -159,7 +175,7 @@ def _run(args) -> int:
     setup_logging(args.log_level)
     from .context import Context
     ctx = Context.from_args(args)
-    why = weight_dtype_refusal(ctx)
+    why = weight_dtype_refusal(ctx) or head_dtype_refusal(ctx)
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

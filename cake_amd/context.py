@@ -42,6 +42,7 @@ class Context:
     max_seq_len: int = 4096
     no_graph: bool = False
     weight_dtype: str = "model"  # --weight-dtype: "fp8" / "mxfp4" = native engine only
+    head_dtype: str = "model"    # --head-dtype: the lm_head's format, native engine only
 
     @classmethod
     def from_args(cls, args) -> "Context":
@@ -67,7 +68,8 @@ class Context:
                    model_path=Path(args.model), model_type=args.model_type, topology=topology,
                    device=device, dtype=dtype, sampling=sampling, max_seq_len=args.max_seq_len,
                    no_graph=getattr(args, "no_graph", False),
-                   weight_dtype=getattr(args, "weight_dtype", "model") or "model")
+                   weight_dtype=getattr(args, "weight_dtype", "model") or "model",
+                   head_dtype=getattr(args, "head_dtype", "model") or "model")
 
 
 def hbm_mib(device=None) -> dict:

@@ -126,6 +126,23 @@ int cake_head_select(int dt, const float* resid, const void* norm_w, float eps, 
                      int K, int N, float* out, int* hist, int* hist_len, int last_n,
                      float penalty, unsigned long long* slot, unsigned int* ticket, int* tok,
                      int* pos, int max_hist, const void* embed, float* emb_out, hipStream_t st);
+// quantised lm_head (gemv_w8_head.hip, gemv_w4_head.hip)
+int cake_gemv_norm_f32_w8(int dt, const float* resid, const void* norm_w, float eps,
+                          const void* w8, const float* scale, int K, int N, float* out,
+                          hipStream_t st);
+int cake_head_select_w8(int dt, const float* resid, const void* norm_w, float eps, const void* w8,
+                        const float* scale, int K, int N, float* out, int* hist, int* hist_len,
+                        int last_n, float penalty, unsigned long long* slot, unsigned int* ticket,
+                        int* tok, int* pos, int max_hist, const void* embed, float* emb_out,
+                        hipStream_t st);
+int cake_gemv_norm_f32_w4(int dt, const float* resid, const void* norm_w, float eps,
+                          const void* w4, const void* e8, int K, int N, float* out,
+                          hipStream_t st);
+int cake_head_select_w4(int dt, const float* resid, const void* norm_w, float eps, const void* w4,
+                        const void* e8, int K, int N, float* out, int* hist, int* hist_len,
+                        int last_n, float penalty, unsigned long long* slot, unsigned int* ticket,
+                        int* tok, int* pos, int max_hist, const void* embed, float* emb_out,
+                        hipStream_t st);
 int cake_repeat_penalty(float* logits, const int* hist, const int* hist_len, int last_n,
                         float penalty, hipStream_t st);
 int cake_argmax(const float* logits, int V, unsigned long long* slot, hipStream_t st);
@@ -323,6 +340,10 @@ const char* const kNoFp8TP =
     "fp8 weights (weight_fmt 1) are not supported with tensor parallelism yet: open the "
     "tensor-parallel engine with weight_fmt 0";
 
+const char* const kNoQHeadTP =
+    "a quantised lm_head (head_fmt 1 = fp8, 2 = mxfp4) is not supported with tensor "
+    "parallelism: open the tensor-parallel engine with head_fmt 0";
+
 Json msg(const char* cmd) {
   Json j = Json::object();
   j.set("cmd", Json::string(cmd));
@@ -337,12 +358,16 @@ class Llama {
   Llama(const std::string& dir, const CakeEngineOpts& o, const CakePipeOpts* pp = nullptr,
         const std::vector<int>* layers = nullptr, const CakeTPOpts* tp = nullptr,
         const CakeRemoteOpts* remote = nullptr)
-      : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), seed_(o.seed) {
+      : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), hfmt_(o.head_fmt),
+        seed_(o.seed) {
     if (dt_ != 0 && dt_ != 1) throw Error("dtype must be 0 (bf16) or 1 (f16)");
     if (wfmt_ != 0 && wfmt_ != 1 && wfmt_ != 2)
       throw Error("weight_fmt must be 0 (model dtype), 1 (fp8 e4m3 projections) or 2 (mxfp4 "
                   "projections)");
     if (wfmt_ != 0 && tp) throw Error(kNoFp8TP);
+    if (hfmt_ != 0 && hfmt_ != 1 && hfmt_ != 2)
+      throw Error("head_fmt must be 0 (model dtype), 1 (fp8 e4m3 lm_head) or 2 (mxfp4 lm_head)");
+    if (hfmt_ != 0 && tp) throw Error(kNoQHeadTP);
     if (init_ != 0 && init_ != 1) throw Error("init must be 0 (checkpoint) or 1 (random)");
     if (tp) {
       tp_ = tp->world;
@@ -391,6 +416,7 @@ class Llama {
     if (wfmt_ == 2 && (cfg_.H % 32 || (cfg_.nh * cfg_.hd) % 32 || cfg_.I % 32))
       throw Error("mxfp4 weights need hidden, attention and intermediate widths divisible by 32");
     if (layers) {  // a TCP worker: the topology node's layers, no embedding / head
+      hfmt_ = 0;   // no head here: the option is accepted and ignored
       owned_ = *layers;
       std::sort(owned_.begin(), owned_.end());
       owned_.erase(std::unique(owned_.begin(), owned_.end()), owned_.end());
@@ -431,7 +457,11 @@ class Llama {
       for (int l = 0; l < cfg_.L; ++l)
         if (owner_[l] == rank_ && (remote_of_.empty() || remote_of_[l] < 0)) owned_.push_back(l);
       head_ = rank_ == 0;
+      if (!head_) hfmt_ = 0;  // the head lives on rank 0: accepted and ignored elsewhere
     }
+    if (hfmt_ == 1 && cfg_.H % 16) throw Error("an fp8 lm_head needs a hidden width divisible by 16");
+    if (hfmt_ == 2 && cfg_.H % 32)
+      throw Error("an mxfp4 lm_head needs a hidden width divisible by 32");
     lo_ = owned_.empty() ? 0 : owned_.front();
     hi_ = owned_.empty() ? 0 : owned_.back() + 1;
     local_.assign(cfg_.L, -1);
@@ -440,12 +470,15 @@ class Llama {
     planner_.load(pkg_dir() + "/ops/gemm_tuned.json");
     load_weights(dir);
     // one line per open: what the weights are and what they occupy
-    std::fprintf(stderr, "cake engine: weights %s, %lld bytes on device (rank %d, %d layers)\n",
+    std::fprintf(stderr,
+                 "cake engine: weights %s, lm_head %s, %lld bytes on device (rank %d, %d layers)\n",
                  wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
                                         : "fp8 e4m3 projections (f16 rest)")
                  : wfmt_ == 2 ? (dt_ == 0 ? "mxfp4 projections (bf16 rest)"
                                           : "mxfp4 projections (f16 rest)")
                               : (dt_ == 0 ? "bf16" : "f16"),
+                 !head_ ? "none" : hfmt_ == 1 ? "fp8 e4m3" : hfmt_ == 2 ? "mxfp4"
+                                                : (dt_ == 0 ? "bf16" : "f16"),
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
@@ -693,8 +726,7 @@ class Llama {
     if (tp_ > 1) {
       head_tp(hidden_ + (size_t)(T - 1) * cfg_.H, mode);
     } else {
-      k_check(cake_gemv_norm_f32(dt_, hidden_ + (size_t)(T - 1) * cfg_.H, norm_, (float)lc_.eps,
-                                 lm_head_, lc_.H, lc_.V, logits_, st_), "lm_head");
+      head_gemv(hidden_ + (size_t)(T - 1) * cfg_.H);
       select_tail(mode);
     }
     if (mode.fused) k_check(cake_embed(dt_, embed_, tok_, 1, cfg_.H, resid_, st_), "embed");
@@ -777,7 +809,13 @@ class Llama {
 
   int dt_, dev_, init_ = 0;
   int wfmt_ = 0;               // CakeEngineOpts.weight_fmt
+  int hfmt_ = 0;               // CakeEngineOpts.head_fmt (0 on a rank without the head)
   int64_t weight_bytes_ = 0;   // device weight allocations of this rank
+  // head_fmt 1: head_q_ holds the e4m3 codes [V, H], head_s_ the f32 row scales; head_fmt 2:
+  // head_q_ the packed e2m1 codes [V, H/2], head_e_ the e8m0 bytes [V, H/32].  lm_head_ is
+  // then null (untied) or the 16-bit embedding (tied: the gather needs it)
+  uint8_t *head_q_ = nullptr, *head_e_ = nullptr;
+  float* head_s_ = nullptr;
   // weight_fmt 1, 2: 16-bit scratch for the largest projection — the loader fills it before
   // each quantise (the 16-bit copy is never kept), prefill dequantises into it before
   // each GEMM
@@ -999,6 +1037,39 @@ class Llama {
     w = w8;
   }
 
+  // head_fmt 1, 2: the 16-bit rows of an untied head go through a temporary [V, H] buffer
+  // (not counted: head_keep frees it before open returns), so the peak of an open is the
+  // resident weights + 2 V H bytes
+  uint16_t* head_stage() {
+    if (hfmt_ == 0) return walloc16((size_t)lc_.V * cfg_.H);
+    return dalloc<uint16_t>((size_t)lc_.V * cfg_.H);
+  }
+  // keep the head rows16 holds: as they are, or quantised (the projections' row quantisers);
+  // `temp`: rows16 is head_stage's buffer and is freed, else it is the resident embedding
+  void head_keep(uint16_t* rows16, bool temp) {
+    if (hfmt_ == 0) {
+      lm_head_ = rows16;
+      return;
+    }
+    const size_t V = lc_.V, H = cfg_.H;
+    if (hfmt_ == 1) {
+      head_q_ = dalloc<uint8_t>(V * H);
+      head_s_ = dalloc<float>(V);
+      weight_bytes_ += (int64_t)(V * H + 4 * V);
+      k_check(cake_quant_rows_fp8(dt_, rows16, (int)V, (int)H, head_q_, head_s_, st_),
+              "quant_rows_fp8 lm_head");
+    } else {
+      head_q_ = dalloc<uint8_t>(V * H / 2);
+      head_e_ = dalloc<uint8_t>(V * H / 32);
+      weight_bytes_ += (int64_t)(V * H / 2 + V * H / 32);
+      k_check(cake_quant_rows_mxfp4(dt_, rows16, (int)V, (int)H, head_q_, head_e_, st_),
+              "quant_rows_mxfp4 lm_head");
+    }
+    hip_check(hipStreamSynchronize(st_), "sync");
+    if (temp) dfree(rows16);
+    else lm_head_ = rows16;
+  }
+
   // weights of this rank: all of the model, its pipeline layers, or (tensor parallel) its
   // slices — q / k / v rows of its heads, o_proj columns of its heads, gate / up rows and
   // down_proj columns of its intermediate range, lm_head rows of its vocabulary range
@@ -1021,10 +1092,11 @@ class Llama {
       norm_ = walloc16(H);
       fill(norm_, H, 1.f, 0.05f, 2);
       if (c.tie && tp_ == 1) {
-        lm_head_ = embed_;
+        head_keep((uint16_t*)embed_, false);
       } else {
-        lm_head_ = walloc16((size_t)lc_.V * H);
-        fill(lm_head_, (size_t)lc_.V * H, 0.f, 0.02f, 3);
+        uint16_t* hw = head_stage();  // the same draws whatever the head format
+        fill(hw, (size_t)lc_.V * H, 0.f, 0.02f, 3);
+        head_keep(hw, true);
       }
     }
     layers_.resize(owned_.size());
@@ -1074,10 +1146,11 @@ class Llama {
           lm_head_ = walloc16((size_t)lc_.V * H);
           upload_slice(ck, hn, lm_head_, voff_, lc_.V, 0, H, stage, stage_bytes);
         } else if (own_head) {
-          lm_head_ = walloc16(V * H);
-          upload(ck, hn, lm_head_, V * H, stage, stage_bytes);
+          uint16_t* hw = head_stage();
+          upload(ck, hn, hw, V * H, stage, stage_bytes);
+          head_keep(hw, true);
         } else {
-          lm_head_ = embed_;  // tied embeddings
+          head_keep((uint16_t*)embed_, false);  // tied embeddings
         }
       }
       layers_.resize(owned_.size());
@@ -1368,9 +1441,7 @@ class Llama {
   // handed rank to rank through the peers' IPC-mapped prefill buffers) -> head
   void prefill(const int32_t* prompt, int T) {
     prefill_body(prompt, T);
-    const Cfg& c = lc_;
-    k_check(cake_gemv_norm_f32(dt_, hidden_ + (size_t)(T - 1) * c.H, norm_, (float)c.eps,
-                               lm_head_, c.H, c.V, logits_, st_), "lm_head");
+    head_gemv(hidden_ + (size_t)(T - 1) * lc_.H);
   }
 
   void prefill_body(const int32_t* prompt, int T) {
@@ -1689,23 +1760,47 @@ class Llama {
       return;
     }
     if (m.fused) {
-      k_check(cake_head_select(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_,
-                               hist_, hist_len_, m.penalty != 1.f ? m.last_n : 0, m.penalty,
-                               slot_, sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
-              "head_select");
+      const int last_n = m.penalty != 1.f ? m.last_n : 0;
+      if (hfmt_ == 1)
+        k_check(cake_head_select_w8(dt_, resid_, norm_, (float)c.eps, head_q_, head_s_, c.H, c.V,
+                                    logits_, hist_, hist_len_, last_n, m.penalty, slot_,
+                                    sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
+                "head_select_w8");
+      else if (hfmt_ == 2)
+        k_check(cake_head_select_w4(dt_, resid_, norm_, (float)c.eps, head_q_, head_e_, c.H, c.V,
+                                    logits_, hist_, hist_len_, last_n, m.penalty, slot_,
+                                    sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
+                "head_select_w4");
+      else
+        k_check(cake_head_select(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_,
+                                 hist_, hist_len_, last_n, m.penalty, slot_, sel_ticket_, tok_,
+                                 pos_, S_, embed_, resid_, st_),
+                "head_select");
       return;
     }
-    k_check(cake_gemv_norm_f32(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
-            "lm_head");
+    head_gemv(resid_);
     select_tail(m);
+  }
+
+  // logits_ = lm_head . rms_norm(row): the 16-bit head or its quantised twin (head_fmt)
+  void head_gemv(const float* row) {
+    const Cfg& c = lc_;
+    if (hfmt_ == 1)
+      k_check(cake_gemv_norm_f32_w8(dt_, row, norm_, (float)c.eps, head_q_, head_s_, c.H, c.V,
+                                    logits_, st_), "lm_head_w8");
+    else if (hfmt_ == 2)
+      k_check(cake_gemv_norm_f32_w4(dt_, row, norm_, (float)c.eps, head_q_, head_e_, c.H, c.V,
+                                    logits_, st_), "lm_head_w4");
+    else
+      k_check(cake_gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
+              "lm_head");
   }
 
   // f32 logits of the whole vocabulary for one hidden row: logits_ (one rank), or this
   // rank's vocabulary shard gathered into full_logits_ on every tensor-parallel rank
   float* head_logits(const float* row) {
     const Cfg& c = lc_;
-    k_check(cake_gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
-            "lm_head");
+    head_gemv(row);
     if (tp_ == 1) return logits_;
     k_check(cake_ar_gather(logits_, voff_, c.V, full_logits_, cfg_.V, ch_gat_.peers.data(),
                            ch_gat_.inbox, ar_seq_ + 4, ar_err_ + 2, tp_rank_, tp_, hop_timeout_,
@@ -2805,6 +2900,7 @@ CAKE_API void* cake_engine_open_tp(const char* model_dir, const CakeEngineOpts* 
   try {
     if (!model_dir || !opts || !tp) throw cake::Error("null argument");
     if (opts->weight_fmt != 0) throw cake::Error(cake::kNoFp8TP);
+    if (opts->head_fmt != 0) throw cake::Error(cake::kNoQHeadTP);
     return new Llama(model_dir, *opts, nullptr, nullptr, tp);
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());

@@ -30,6 +30,12 @@ struct CakeEngineOpts {
                             // byte + one e8m0 scale byte per 32 elements of a row; widths
                             // divisible by 32), quantised on load.  1, 2: not with open_tp.
   uint64_t seed;            // init = 1: weight seed
+  int32_t head_fmt;         // 0: lm_head in the model dtype; 1: e4m3fn codes + one f32 scale per
+                            // vocabulary row; 2: MXFP4 (hidden width divisible by 32).  Chosen
+                            // independently of weight_fmt; quantised on load with the
+                            // projections' row quantisers.  The embedding stays 16-bit (tied:
+                            // the quantised head is an extra allocation).  Ranks and workers
+                            // without the head ignore it.  1, 2: not with open_tp.
 };
 
 // Layer-sharded pipeline over one process per GPU.  Placement: `owners[l]` is the rank
@@ -126,7 +132,8 @@ int32_t cake_engine_info(void* engine, int32_t* out8);
 // EOS ids of the config (up to cap); returns the count
 int32_t cake_engine_eos(void* engine, int32_t* out, int32_t cap);
 // bytes of this rank's device weight allocations: embedding, head if untied, norms,
-// projections and their scales (weight_fmt 1: f32 per row; 2: one byte per 32 elements)
+// projections and their scales (weight_fmt 1: f32 per row; 2: one byte per 32 elements),
+// the quantised head and its scales (head_fmt 1, 2: also when the embeddings are tied)
 int64_t cake_engine_weight_bytes(void* engine);
 // Prefill `prompt` from position 0, then generate up to max_new tokens (the first comes
 // from the prefill logits), stopping after an EOS id.  Tokens go to out[] (and cb).

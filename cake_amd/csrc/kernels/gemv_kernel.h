@@ -524,6 +524,93 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_kernel(
   }
 }
 
+// The SEL pieces of gemv_norm_f32_kernel as helpers, shared by its quantised twins
+// (gemv_norm_f32_w8_kernel, gemv_norm_f32_w4_kernel).  The 16-bit kernel keeps its own
+// inline copy: its code generation is the measured baseline of the default path.
+
+// the lane's share of the penalty window (4 tokens per lane, -1 = none)
+__device__ __forceinline__ void head_sel_window(const HeadSel& hs, int hlen, int lane, int* win) {
+  const int n = min(hs.last_n, hlen), start = hlen - n;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) win[j] = j * 64 + lane < n ? hs.hist[start + j * 64 + lane] : -1;
+}
+
+// penalty on the pair's (wave-uniform) logits and the running best key of the wave
+__device__ __forceinline__ void head_sel_pair(const HeadSel& hs, const int* win, int ra, int rb,
+                                              int N, float& da, float& db,
+                                              unsigned long long& best) {
+  if (hs.penalty != 1.f) {
+    const bool ia = win[0] == ra || win[1] == ra || win[2] == ra || win[3] == ra;
+    const bool ib = win[0] == rb || win[1] == rb || win[2] == rb || win[3] == rb;
+    if (__builtin_amdgcn_ballot_w64(ia) != 0ull) da = da >= 0.f ? da / hs.penalty : da * hs.penalty;
+    if (__builtin_amdgcn_ballot_w64(ib) != 0ull) db = db >= 0.f ? db / hs.penalty : db * hs.penalty;
+  }
+  const unsigned long long ka =
+      ((unsigned long long)ordered_key(da) << 32) | (0xffffffffu - (unsigned int)ra);
+  best = ka > best ? ka : best;
+  if (rb < N) {
+    const unsigned long long kb =
+        ((unsigned long long)ordered_key(db) << 32) | (0xffffffffu - (unsigned int)rb);
+    best = kb > best ? kb : best;
+  }
+}
+
+// block max -> one returning 8-byte device atomic on the slot, drained before the ticket;
+// the last workgroup finalizes the step and gathers the next input row (16-bit table).
+// Its words live in `lds`, the start of the kernel's dynamic LDS (the x row, dead after the
+// pair loop; >= 64 bytes), not in static __shared__ variables: those sit in front of the
+// dynamic region, and the 40 bytes they took left its base 8 bytes off a 16-byte boundary,
+// which made every ds_read_b128 of x in the pair loop an unaligned (replayed) access.
+template <int DT>
+__device__ __forceinline__ void head_sel_tail(const HeadSel& hs, unsigned long long best,
+                                              void* lds) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  unsigned long long* red = reinterpret_cast<unsigned long long*>(lds);  // [kGemvWaves]
+  int& is_last = reinterpret_cast<int*>(lds)[2 * kGemvWaves];
+  int& sel_tok = reinterpret_cast<int*>(lds)[2 * kGemvWaves + 1];
+  __syncthreads();  // every wave has read its last x
+  if (lane == 0) red[wave] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long b = red[0];
+#pragma unroll
+    for (int i = 1; i < kGemvWaves; ++i) b = red[i] > b ? red[i] : b;
+    const unsigned long long old =
+        __hip_atomic_fetch_max(hs.slot, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::"v"((unsigned int)old) : "memory");
+    const unsigned int t =
+        __hip_atomic_fetch_add(hs.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = t == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (is_last) {  // block-uniform
+    if (threadIdx.x == 0) {
+      const unsigned long long key =
+          __hip_atomic_fetch_max(hs.slot, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int t = (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull));
+      *hs.tok = t;
+      const int len = *hs.hist_len_w;
+      if (len < hs.max_hist) { hs.hist_w[len] = t; *hs.hist_len_w = len + 1; }
+      *hs.pos += 1;
+      // re-arm for the next launch (the kernel boundary orders these for it)
+      __hip_atomic_store(hs.slot, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(hs.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sel_tok = t;
+    }
+    if (hs.embed != nullptr) {
+      // every other workgroup has finished reading resid (their tickets preceded this one)
+      __syncthreads();
+      const uint16_t* row = hs.embed + (size_t)sel_tok * hs.H;
+      for (int i = threadIdx.x * 8; i < hs.H; i += kGemvThreads * 8) {
+        float f[8];
+        unpack8<DT>(*reinterpret_cast<const uint4*>(row + i), f);
+        *reinterpret_cast<float4*>(hs.emb_out + i) = make_float4(f[0], f[1], f[2], f[3]);
+        *reinterpret_cast<float4*>(hs.emb_out + i + 4) = make_float4(f[4], f[5], f[6], f[7]);
+      }
+    }
+  }
+}
+
 // Launch geometry per kernel kind (tunable at run time; defaults from the
 // rocprofv3-measured sweep in profiles/): U = chunks in flight per row,
 // PF = prefetch the first weight batch before the x prologue, MB = grid cap.

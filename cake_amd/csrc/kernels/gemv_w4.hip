@@ -10,8 +10,9 @@ namespace cake {
 // decode graph, one kind varied at a time (profiles/mxfp4_decode_tuning_sweep.jsonl): the
 // prefetch is worth 4-8 % ms/token per kind, the SwiGLU cap of 1024 beats 512 and 2048;
 // every other variation stayed under twice the 1.2 % spread of the default (x16 at U = 1
-// was -1.4 to -2 %) and was not adopted.  Nothing was swept at 70B.
-GemvTune g_tune_w4[kNumW4Kinds] = {{2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}};
+// was -1.4 to -2 %) and was not adopted.  Nothing was swept at 70B.  The fourth kind is the
+// quantised lm_head (gemv_w4_head.hip), started from the SwiGLU values.
+GemvTune g_tune_w4[kNumW4Kinds] = {{2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}};
 }  // namespace cake
 
 CAKE_API int cake_gemv_w4_set_tuning(int kind, int U, int prefetch, int max_blocks) {

@@ -1,7 +1,7 @@
 // Decode GEMV kernels over MXFP4 weight-only projections: the 4-bit twins of
-// qkv_rope_kernel / swiglu_kernel / gemv_x16_kernel (gemv_kernel.h), shared by
-// gemv_w4.hip, gemv_w4_mlp.hip and gemv_w4_x16.hip (one launcher per translation unit so
-// the instantiations compile in parallel).
+// qkv_rope_kernel / swiglu_kernel / gemv_x16_kernel / gemv_norm_f32_kernel (gemv_kernel.h),
+// shared by gemv_w4.hip, gemv_w4_mlp.hip, gemv_w4_x16.hip and gemv_w4_head.hip (one launcher
+// per translation unit so the instantiations compile in parallel).
 //
 // Format (quant_mxfp4.hip writes it): w4[N, K/2] two e2m1 codes per byte (k even in the low
 // nibble), e8[N, K/32] one e8m0 scale byte per 32 consecutive k,
@@ -403,11 +403,56 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_x16_w4_kernel(
   run_pairs_w4<DT, false, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
 }
 
-// Launch geometry of the three MXFP4 launchers (their own table).  A row is K / 32 chunks:
+// ---------------------------------------------------------------------------
+// RMSNorm(f32 row) then f32 output over MXFP4 rows: the quantised lm_head, the 4-bit twin
+// of gemv_norm_f32_kernel (SEL: + greedy selection, see HeadSel; the next input row comes
+// from the 16-bit embedding table).  run_pairs_w4 delivers scaled sums, so the epilogue and
+// tail are the 16-bit kernel's.
+// ---------------------------------------------------------------------------
+template <int DT, int U, int PFC, int NX, bool SEL>
+__global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_w4_kernel(
+    const float* __restrict__ resid, const uint16_t* __restrict__ norm_w, float eps,
+    const uint8_t* __restrict__ w, const uint8_t* __restrict__ e8, int K, int N,
+    float* __restrict__ out, HeadSel hs) {
+  extern __shared__ float xs[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int npairs = (N + 1) >> 1;
+  const int p0 = blockIdx.x * kGemvWaves + wave;
+  const size_t rowb = (size_t)K >> 1, rowe = (size_t)K >> 5;
+  auto map = [&](int p) {
+    const size_t ra = (size_t)(2 * p), rb = (size_t)min(2 * p + 1, N - 1);
+    return RowsW4{w + ra * rowb, w + rb * rowb, e8 + ra * rowe, e8 + rb * rowe};
+  };
+  int hlen = 0;
+  if constexpr (SEL) hlen = hs.penalty != 1.f ? *hs.hist_len : 0;
+  RegsW4<PFC> pre;
+  NormPreW4<DT, NX> xp;
+  const RowsW4 r0 = map(p0 < npairs ? p0 : npairs - 1);
+  if constexpr (NX > 0) xp.load(resid, norm_w, K);
+  __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
+  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows_w4<PFC>(r0, pre);  // NX: exact vmcnt
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (NX > 0) xp.finish(eps, K, xs);
+  else stage_rmsnorm_perm4<DT>(resid, norm_w, eps, K, xs);
+  int win[4] = {-1, -1, -1, -1};
+  if constexpr (SEL) head_sel_window(hs, hlen, lane, win);
+  unsigned long long best = 0ull;
+  auto epi = [&](int p, float da, float db) {
+    const int ra = 2 * p, rb = 2 * p + 1;
+    if constexpr (SEL) head_sel_pair(hs, win, ra, rb, N, da, db, best);
+    if (lane != 0) return;
+    out[ra] = da;
+    if (rb < N) out[rb] = db;
+  };
+  run_pairs_w4<DT, true, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
+  if constexpr (SEL) head_sel_tail<DT>(hs, best, xs);
+}
+
+// Launch geometry of the MXFP4 launchers (their own table).  A row is K / 32 chunks:
 // 8B's K = 4096 is 2 per lane, 70B's K = 8192 is 4, the down projections 7 and 14.  So the
 // prefetch depths are PF in {0, 2, 4} chunks per row per lane (2 = the whole row of an 8B
 // hidden-width projection, 4 = of a 70B one) and U in {1, 2, 4} for what follows it.
-enum GemvW4Kind { kQkvW4 = 0, kSwigluW4 = 1, kX16W4 = 2, kNumW4Kinds = 3 };
+enum GemvW4Kind { kQkvW4 = 0, kSwigluW4 = 1, kX16W4 = 2, kHeadW4 = 3, kNumW4Kinds = 4 };
 extern GemvTune g_tune_w4[kNumW4Kinds];  // defined in gemv_w4.hip (cake_gemv_w4_set_tuning)
 
 }  // namespace cake

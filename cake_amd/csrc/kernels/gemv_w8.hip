@@ -9,8 +9,9 @@ namespace cake {
 // 8B decode graph, one kind varied at a time (profiles/fp8_decode_tuning_sweep.jsonl):
 // SwiGLU at a 1024-block cap is -3..-5 % ms/token against the 16-bit twin's 512 (rows
 // are half as long, so a wave's fixed prologue weighs twice as much per pair); every
-// other variation stayed inside the 2 % engine-to-engine spread of that sweep
-GemvTune g_tune_w8[kNumW8Kinds] = {{2, 4, 1024}, {2, 4, 1024}, {4, 4, 1024}};
+// other variation stayed inside the 2 % engine-to-engine spread of that sweep.  The fourth
+// kind is the quantised lm_head (gemv_w8_head.hip), started from the SwiGLU values
+GemvTune g_tune_w8[kNumW8Kinds] = {{2, 4, 1024}, {2, 4, 1024}, {4, 4, 1024}, {2, 4, 1024}};
 }  // namespace cake
 
 CAKE_API int cake_gemv_w8_set_tuning(int kind, int U, int prefetch, int max_blocks) {

@@ -1,7 +1,7 @@
 // Decode GEMV kernels over FP8 (OCP e4m3fn) weight-only projections: the 8-bit twins of
-// qkv_rope_kernel / swiglu_kernel / gemv_x16_kernel (gemv_kernel.h), shared by
-// gemv_w8.hip, gemv_w8_mlp.hip and gemv_w8_x16.hip (one launcher per translation unit so
-// the instantiations compile in parallel).
+// qkv_rope_kernel / swiglu_kernel / gemv_x16_kernel / gemv_norm_f32_kernel (gemv_kernel.h),
+// shared by gemv_w8.hip, gemv_w8_mlp.hip, gemv_w8_x16.hip and gemv_w8_head.hip (one launcher
+// per translation unit so the instantiations compile in parallel).
 //
 // Format: w8[N, K] one e4m3fn code per element, scale[N] f32 per output row,
 // W[n, k] = scale[n] * fp8(w8[n, k])  (quant_fp8.hip writes it).  K % 16 == 0.
@@ -376,10 +376,63 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_x16_w8_kernel(
   run_pairs_w8<DT, false, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
 }
 
-// Launch geometry of the three fp8 launchers (their own table: a row is half the bytes of
+// ---------------------------------------------------------------------------
+// RMSNorm(f32 row) then f32 output over fp8 rows: the quantised lm_head, the 8-bit twin of
+// gemv_norm_f32_kernel (SEL: + greedy selection, see HeadSel; the next input row comes
+// from the 16-bit embedding table)
+// ---------------------------------------------------------------------------
+template <int DT, int U, int PFC, int NX, bool SEL>
+__global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_w8_kernel(
+    const float* __restrict__ resid, const uint16_t* __restrict__ norm_w, float eps,
+    const uint8_t* __restrict__ w, const float* __restrict__ scale, int K, int N,
+    float* __restrict__ out, HeadSel hs) {
+  extern __shared__ float xs[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int npairs = (N + 1) >> 1;
+  const int p0 = blockIdx.x * kGemvWaves + wave;
+  auto map = [&](int p, const uint8_t*& wa, const uint8_t*& wb) {
+    wa = w + (size_t)(2 * p) * K;
+    wb = w + (size_t)min(2 * p + 1, N - 1) * K;
+  };
+  // SEL: the history length ahead of the x prologue, the window after it (as the 16-bit
+  // kernel)
+  int hlen = 0;
+  if constexpr (SEL) hlen = hs.penalty != 1.f ? *hs.hist_len : 0;
+  Regs<PFC> pre;
+  NormPreW8<DT, NX> xp;
+  const int pc = p0 < npairs ? p0 : npairs - 1;
+  const uint8_t *wa0, *wb0;
+  map(pc, wa0, wb0);
+  if constexpr (NX > 0) xp.load(resid, norm_w, K);
+  __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
+  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows_w8<PFC>(wa0, wb0, pre);  // NX: exact vmcnt
+  // the first pair's row scales, requested now (one address per wave: every lane holds
+  // the value, which the SEL ballot and key need wave-wide)
+  const float s0a = scale[2 * pc], s0b = scale[min(2 * pc + 1, N - 1)];
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (NX > 0) xp.finish(eps, K, xs);
+  else stage_rmsnorm_perm<DT>(resid, norm_w, eps, K, xs);
+  int win[4] = {-1, -1, -1, -1};
+  if constexpr (SEL) head_sel_window(hs, hlen, lane, win);
+  unsigned long long best = 0ull;
+  auto epi = [&](int p, float da, float db) {
+    const int ra = 2 * p, rb = 2 * p + 1;
+    // the row scales first: everything below sees the logits
+    da *= p == p0 ? s0a : scale[ra];
+    db *= p == p0 ? s0b : scale[min(rb, N - 1)];
+    if constexpr (SEL) head_sel_pair(hs, win, ra, rb, N, da, db, best);
+    if (lane != 0) return;
+    out[ra] = da;
+    if (rb < N) out[rb] = db;
+  };
+  run_pairs_w8<DT, true, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
+  if constexpr (SEL) head_sel_tail<DT>(hs, best, xs);
+}
+
+// Launch geometry of the fp8 launchers (their own table: a row is half the bytes of
 // its 16-bit twin — 8B's K = 4096 is 4 chunks per lane — so the 16-bit tuning does not
 // carry over).  U in {1, 2, 4}, PF in {0, 2, 4} chunks per row per lane.
-enum GemvW8Kind { kQkvW8 = 0, kSwigluW8 = 1, kX16W8 = 2, kNumW8Kinds = 3 };
+enum GemvW8Kind { kQkvW8 = 0, kSwigluW8 = 1, kX16W8 = 2, kHeadW8 = 3, kNumW8Kinds = 4 };
 extern GemvTune g_tune_w8[kNumW8Kinds];  // defined in gemv_w8.hip (cake_gemv_w8_set_tuning)
 
 }  // namespace cake

@@ -105,6 +105,10 @@ const Flag kFlags[] = {
      "native Llama engine: fp8 = e4m3 per-layer projections with one scale per row, mxfp4 = "
      "e2m1 projections with one power-of-two scale per 32 elements, both quantised on load "
      "(not with --parallel tp); model = --dtype"},
+    {"--head-dtype", "head_dtype", PyArg::kStr, "model", "model|fp8|mxfp4", false,
+     "native Llama engine: the lm_head as fp8 (e4m3, one scale per vocabulary row) or mxfp4, "
+     "quantised on load, chosen independently of --weight-dtype (not with --parallel tp; "
+     "workers hold no head and ignore it); model = --dtype"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -188,7 +192,8 @@ int env_int(const char* k, int def) {
   return v ? std::atoi(v) : def;
 }
 
-// --weight-dtype -> CakeEngineOpts.weight_fmt (the choices are checked by the parser)
+// --weight-dtype / --head-dtype -> CakeEngineOpts.weight_fmt / head_fmt (the choices are
+// checked by the parser)
 int32_t weight_fmt_of(const std::string& v) { return v == "fp8" ? 1 : (v == "mxfp4" ? 2 : 0); }
 
 struct StreamCtx {
@@ -297,6 +302,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     CakeEngineOpts eo{(int32_t)num("max_seq_len", 4096), o["dtype"].value == "bf16" ? 0 : 1,
                       env_int("LOCAL_RANK", rank), 1};
     eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
+    eo.head_fmt = weight_fmt_of(o["head_dtype"].value);  // pp: ignored off rank 0; tp: refused
     CakePipeOpts po{rank, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
                     owners.empty() ? nullptr : owners.data(), (int32_t)owners.size()};
     CakeTPOpts to{rank, world, ctl.c_str(), 60.0, 600.0};
@@ -334,6 +340,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   eo.device = pipe ? env_int("LOCAL_RANK", 0) : (int32_t)num("device", 0);
   eo.steps_per_graph = 1;
   eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
+  eo.head_fmt = weight_fmt_of(o["head_dtype"].value);
   char err[1024] = {0};
   const auto t0 = std::chrono::steady_clock::now();
   CakePipeOpts po{0, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,

@@ -24,7 +24,7 @@ TOKEN_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
 class EngineOpts(C.Structure):
     _fields_ = [("max_seq", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("steps_per_graph", C.c_int32), ("init", C.c_int32), ("weight_fmt", C.c_int32),
-                ("seed", C.c_uint64)]
+                ("seed", C.c_uint64), ("head_fmt", C.c_int32)]
 
 
 class PipeOpts(C.Structure):
@@ -57,7 +57,7 @@ class EngineStats(C.Structure):
                 ("p99_ms", C.c_float)]
 
 
-# CakeEngineOpts.weight_fmt
+# CakeEngineOpts.weight_fmt and .head_fmt
 WEIGHT_FORMATS = {"model": 0, "fp8": 1, "mxfp4": 2}
 
 _lib = None
@@ -135,7 +135,7 @@ class NativeLlama:
                  tp: bool = False, owners: list[int] | None = None, random_init: bool = False,
                  seed: int = 0, worker_of: list[int] | None = None,
                  workers: list[str] | None = None, remote_timeout_s: float = 120.0,
-                 weights: str = "model"):
+                 weights: str = "model", head: str = "model"):
         """world > 1: one rank of a layer-sharded pipeline, or with tp=True of a tensor-
         parallel group (rank 0 generates; the others call :meth:`serve`).  Every rank of
         one group must be constructed concurrently.  ``owners`` (pipeline): the rank of
@@ -150,16 +150,25 @@ class NativeLlama:
         scale per output row, quantised on load (embedding, lm_head, norms and the KV cache
         stay in ``dtype``); "mxfp4" stores them as OCP MXFP4, two e2m1 codes per byte with one
         power-of-two scale byte per 32 elements of a row (widths divisible by 32), also
-        quantised on load.  Neither is available with ``tp=True``."""
+        quantised on load.  Neither is available with ``tp=True``.
+        ``head``: the lm_head's format, chosen independently of ``weights``: "model", "fp8"
+        (e4m3fn codes and one f32 scale per vocabulary row) or "mxfp4" (hidden width
+        divisible by 32), quantised on load.  The embedding stays in ``dtype``; with tied
+        embeddings the quantised head is an extra allocation.  Ranks without the head ignore
+        it; not available with ``tp=True``."""
         if dtype not in ("bf16", "f16"):
             raise ValueError("native engine dtype: bf16 or f16")
         if weights not in WEIGHT_FORMATS:
             raise ValueError(f"native engine weights: one of {sorted(WEIGHT_FORMATS)}, "
                              f"got {weights!r}")
+        if head not in WEIGHT_FORMATS:
+            raise ValueError(f"native engine head: one of {sorted(WEIGHT_FORMATS)}, got {head!r}")
         self.weights = weights
+        self.head = head
         opts = EngineOpts(int(max_seq), 0 if dtype == "bf16" else 1, int(device),
                           max(1, int(steps_per_graph)), 1 if random_init else 0,
-                          WEIGHT_FORMATS[weights], int(seed) & 0xFFFFFFFFFFFFFFFF)
+                          WEIGHT_FORMATS[weights], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                          WEIGHT_FORMATS[head])
         err = C.create_string_buffer(1024)
         self._h = None
         if world > 1 and tp:
@@ -207,7 +216,8 @@ class NativeLlama:
     def weight_bytes(self) -> int:
         """Bytes of this rank's device weight allocations: embedding, head if untied,
         norms, projections and their scales (``weights="fp8"``: one f32 per row;
-        ``"mxfp4"``: one byte per 32 elements)."""
+        ``"mxfp4"``: one byte per 32 elements), and a quantised head with its scales
+        (``head="fp8"`` / ``"mxfp4"``; counted also when the embeddings are tied)."""
         return int(lib().cake_engine_weight_bytes(self._h))
 
     def walk(self) -> str:

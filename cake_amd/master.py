@@ -146,6 +146,9 @@ def _load_text(ctx):
     if getattr(ctx, "weight_dtype", "model") != "model":
         from .cli import needs_native
         raise RuntimeError(needs_native(ctx.weight_dtype))
+    if getattr(ctx, "head_dtype", "model") != "model":
+        from .cli import needs_native
+        raise RuntimeError(needs_native(ctx.head_dtype, "--head-dtype"))
     from .models.llama3.generator import LLamaGenerator
     return LLamaGenerator.load(ctx)
 

@@ -54,7 +54,8 @@ class NativeLLM(TextGenerator):
                     kw = dict(worker_of=worker_of, workers=workers)
             engine = NativeLlama(ctx.model_path, max_seq=ctx.max_seq_len,
                                  dtype=_dtype_name(ctx.dtype), device=ctx.device.index or 0,
-                                 weights=getattr(ctx, "weight_dtype", "model"), **kw)
+                                 weights=getattr(ctx, "weight_dtype", "model"),
+                                 head=getattr(ctx, "head_dtype", "model"), **kw)
         tok, eos = load_tokenizer(ctx.model_path, engine.eos_ids)
         return cls(engine, tok, eos, ctx.sampling)
 

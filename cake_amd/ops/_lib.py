@@ -160,6 +160,10 @@ _SIGS.update({
     "cake_qkv_rope_w8": [I, P, P, F, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P],
     "cake_swiglu_w8": [I, P, P, F, P, P, P, P, I, I, P, P],
     "cake_gemv_x16_w8": [I, P, P, P, I, I, P, I, P],
+    "cake_gemv_norm_f32_w8": [I, P, P, F, P, P, I, I, P, P],
+    "cake_head_select_w8": [I, P, P, F, P, P, I, I, P, P, P, I, F, P, P, P, P, I, P, P, P],
+    "cake_gemv_norm_f32_w4": [I, P, P, F, P, P, I, I, P, P],
+    "cake_head_select_w4": [I, P, P, F, P, P, I, I, P, P, P, I, F, P, P, P, P, I, P, P, P],
     "cake_gemv_w8_set_tuning": [I, I, I, I],
     "cake_gemv_w8_get_tuning": [I, P],
 })

@@ -771,7 +771,54 @@ def gemv_w8(x, w8, scale, out, accumulate: bool):
                                      int(accumulate), _stream()), "gemv_x16_w8")
 
 
-GEMV_W8_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2}
+def norm_gemv_f32_w8(resid, norm_w, eps, w8, scale, out):
+    """out (f32) = (scale * fp8(w8)) @ rmsnorm(resid)  — the fp8 lm_head (batch 1)."""
+    N, K = w8.shape
+    _req_w8(w8, scale, "w8", (N, K))
+    _dt(norm_w)
+    _req(resid, "resid", dtype=torch.float32, numel=K)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_norm_f32_w8(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(w8),
+                                          _p(scale), K, N, _p(out), _stream()),
+          "gemv_norm_f32_w8")
+
+
+def _head_select_q(entry: str, qa, qb, resid, norm_w, eps, N, K, logits, hist, hist_len, last_n,
+                   penalty, slot, ticket, tok, pos, embed) -> None:
+    """:func:`head_select` over a quantised head (qa, qb = codes and scales); `embed` stays
+    the 16-bit table."""
+    _req(resid, "resid", dtype=torch.float32, numel=K)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req(logits, "logits", dtype=torch.float32, numel=N)
+    _req(slot, "slot", dtype=torch.int64, numel=1)
+    _req(ticket, "ticket", dtype=torch.int32, numel=1)
+    for t, n in ((tok, "tok"), (hist, "hist"), (hist_len, "hist_len"), (pos, "pos")):
+        _req(t, n, dtype=torch.int32)
+    if not 0 <= int(last_n) <= HEAD_SELECT_MAX_LAST_N:
+        raise ValueError(f"{entry}: last_n {last_n} > {HEAD_SELECT_MAX_LAST_N}")
+    if embed is not None:
+        _req(embed, "embed", dtype=norm_w.dtype)
+        if embed.dim() != 2 or embed.shape[1] != K:
+            raise ValueError(f"{entry}: embed {tuple(embed.shape)} does not match H={K}")
+    check(getattr(kernels(), "cake_" + entry)(
+        _dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(qa), _p(qb), K, N, _p(logits),
+        _p(hist), _p(hist_len), int(last_n), float(penalty), _p(slot), _p(ticket), _p(tok),
+        _p(pos), hist.numel(), None if embed is None else _p(embed),
+        None if embed is None else _p(resid), _stream()), entry)
+
+
+def head_select_w8(resid, norm_w, eps, w8, scale, logits, hist, hist_len, last_n: int,
+                   penalty: float, slot, ticket, tok, pos, embed=None) -> None:
+    """:func:`head_select` with the fp8 head (w8 codes + f32 row scales): the penalty and
+    the argmax see the scaled logits."""
+    N, K = w8.shape
+    _req_w8(w8, scale, "w8", (N, K))
+    _head_select_q("head_select_w8", w8, scale, resid, norm_w, eps, N, K, logits, hist, hist_len,
+                   last_n, penalty, slot, ticket, tok, pos, embed)
+
+
+GEMV_W8_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2, "head": 3}
 
 
 def set_gemv_w8_tuning(kind: str, U: int = 4, prefetch: int = 4, max_blocks: int = 1024) -> None:
@@ -868,7 +915,29 @@ def gemv_w4(x, w4, e8, out, accumulate: bool):
                                      int(accumulate), _stream()), "gemv_x16_w4")
 
 
-GEMV_W4_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2}
+def norm_gemv_f32_w4(resid, norm_w, eps, w4, e8, out):
+    """out (f32) = mxfp4(w4, e8) @ rmsnorm(resid)  — the MXFP4 lm_head (batch 1)."""
+    N, K = w4.shape[0], w4.shape[1] * 2
+    _req_w4(w4, e8, "w4", (N, K))
+    _dt(norm_w)
+    _req(resid, "resid", dtype=torch.float32, numel=K)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_norm_f32_w4(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(w4),
+                                          _p(e8), K, N, _p(out), _stream()),
+          "gemv_norm_f32_w4")
+
+
+def head_select_w4(resid, norm_w, eps, w4, e8, logits, hist, hist_len, last_n: int,
+                   penalty: float, slot, ticket, tok, pos, embed=None) -> None:
+    """:func:`head_select` with the MXFP4 head (w4 codes + e8m0 block-scale bytes)."""
+    N, K = w4.shape[0], w4.shape[1] * 2
+    _req_w4(w4, e8, "w4", (N, K))
+    _head_select_q("head_select_w4", w4, e8, resid, norm_w, eps, N, K, logits, hist, hist_len,
+                   last_n, penalty, slot, ticket, tok, pos, embed)
+
+
+GEMV_W4_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2, "head": 3}
 
 
 def set_gemv_w4_tuning(kind: str, U: int = 2, prefetch: int = 4, max_blocks: int = 1024) -> None:

@@ -360,7 +360,8 @@ def _native_rank_engine(ctx, rank: int, world: int, tp: bool):
     return NativeLlama(ctx.model_path, max_seq=ctx.max_seq_len, dtype=_dtype_name(ctx.dtype),
                        device=local, rank=rank, world=world, master_addr=addr,
                        hop_bf16=getattr(a, "hop_dtype", "f32") == "bf16", hop_timeout_s=timeout,
-                       tp=tp, owners=owners, weights=getattr(ctx, "weight_dtype", "model"))
+                       tp=tp, owners=owners, weights=getattr(ctx, "weight_dtype", "model"),
+                       head=getattr(ctx, "head_dtype", "model"))
 
 
 def _native_group(ctx) -> bool:
@@ -417,6 +418,9 @@ def run_rccl(ctx) -> None:
         if getattr(ctx, "weight_dtype", "model") != "model":
             from ..cli import needs_native
             raise RuntimeError(needs_native(ctx.weight_dtype))
+        if getattr(ctx, "head_dtype", "model") != "model":
+            from ..cli import needs_native
+            raise RuntimeError(needs_native(ctx.head_dtype, "--head-dtype"))
         ctx.args.hop = "dist"  # the fallback transport: RCCL p2p / all-reduce
         ctx.args.allreduce = "dist"
     if getattr(ctx.args, "parallel", "pp") == "tp":
