@@ -96,6 +96,11 @@ def build_parser() -> argparse.ArgumentParser:
       help="native Llama engine: the lm_head as fp8 (e4m3 codes, one scale per vocabulary "
            "row) or mxfp4, quantised on load, chosen independently of --weight-dtype (not "
            "with --parallel tp; workers hold no head and ignore it); model = --dtype")
+    a("--kv-dtype", choices=["model", "fp8"], default="model",
+      help="native Llama engine: fp8 = the KV cache as one e4m3 code per element, no scale "
+           "(half the cache; every attention read sees the quantised values), chosen "
+           "independently of --weight-dtype / --head-dtype (not with --parallel tp; each "
+           "worker's own flag governs its own caches); model = --dtype")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -124,11 +129,12 @@ def run_parsed(opts: dict) -> int:
 
 
 def needs_native(fmt: str, flag: str = "--weight-dtype") -> str:
-    """The refusal of a quantised ``--weight-dtype`` / ``--head-dtype`` (fp8, mxfp4) on a
-    Python engine path."""
+    """The refusal of a quantised ``--weight-dtype`` / ``--head-dtype`` / ``--kv-dtype`` (fp8,
+    mxfp4) on a Python engine path."""
+    what = "KV cache" if flag == "--kv-dtype" else "weights"
     return (f"{flag} {fmt} is served by the native Llama engine only (a GPU, "
             "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
-            f"take the Python path, which has no {fmt} weights: refusing rather than "
+            f"take the Python path, which has no {fmt} {what}: refusing rather than "
             "running 16-bit")
 
 
@@ -167,6 +173,12 @@ def head_dtype_refusal(ctx) -> str | None:
     return _quant_refusal(ctx, "--head-dtype", getattr(ctx, "head_dtype", "model"))
 
 
+def kv_dtype_refusal(ctx) -> str | None:
+    """The same for ``--kv-dtype``, in the same wording (a native worker keeps its own
+    caches, so ``cake-cli --mode worker`` serves it; the Python worker refuses)."""
+    return _quant_refusal(ctx, "--kv-dtype", getattr(ctx, "kv_dtype", "model"))
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -175,7 +187,7 @@ def _run(args) -> int:
     setup_logging(args.log_level)
     from .context import Context
     ctx = Context.from_args(args)
-    why = weight_dtype_refusal(ctx) or head_dtype_refusal(ctx)
+    why = weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

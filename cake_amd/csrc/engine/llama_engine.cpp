@@ -58,9 +58,6 @@ int cake_fill_normal(int dt, void* dst, size_t n, float mean, float std, unsigne
 int cake_embed(int dt, const void* table, const int* tok, int T, int H, float* out, hipStream_t st);
 int cake_rmsnorm(int dt, const float* x, const void* w, float eps, int T, int H, void* out,
                  hipStream_t st);
-int cake_rope_kv(int dt, void* q, const void* k, const void* v, int ldq, int ld, int T, int nh,
-                 int nkv, int hd, const float* inv_freq, int pos0, int S, void* kc, void* vc,
-                 hipStream_t st);
 int cake_flash_attn(int dt, const void* q, const void* k, const void* v, void* o, int B, int H,
                     int Hkv, int N, int M, int D, const long long* strides, float scale,
                     int causal, int pos0, hipStream_t st);
@@ -72,10 +69,6 @@ int cake_blaslt_gemm(int dt, int out, const void* a, long long lda, const void* 
                      void* c, long long ldc, int M, int N, int K, void* ws, size_t ws_bytes,
                      hipStream_t st);
 int cake_silu_mul_rows(int dt, const void* gu, size_t T, int I, void* out, hipStream_t st);
-int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
-                  const void* wk, const void* wv, int K, int nh, int nkv, int hd,
-                  const float* inv_freq, const int* pos, float* q_out, void* kcache,
-                  void* vcache, int S, hipStream_t st);
 int cake_attn_decode(int dt, const float* q, const void* kc, const void* vc, const int* pos,
                      int S, int nh, int nkv, int hd, float scale, float* part,
                      unsigned int* tickets, void* out, hipStream_t st);
@@ -95,11 +88,6 @@ int cake_quant_rows_fp8(int dt, const void* w16, int N, int K, void* w8, float* 
                         hipStream_t st);
 int cake_dequant_rows_fp8(int dt, const void* w8, const float* scale, int N, int K, void* out16,
                           hipStream_t st);
-int cake_qkv_rope_w8(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
-                     const void* wk, const void* wv, const float* sq, const float* sk,
-                     const float* sv, int K, int nh, int nkv, int hd, const float* inv_freq,
-                     const int* pos, float* q_out, void* kcache, void* vcache, int S,
-                     hipStream_t st);
 int cake_swiglu_w8(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
                    const void* wu, const float* sg, const float* su, int K, int I, void* act,
                    hipStream_t st);
@@ -110,16 +98,36 @@ int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void*
                           hipStream_t st);
 int cake_dequant_rows_mxfp4(int dt, const void* w4, const void* e8, int N, int K, void* out16,
                             hipStream_t st);
-int cake_qkv_rope_w4(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
-                     const void* wk, const void* wv, const void* eq, const void* ek,
-                     const void* ev, int K, int nh, int nkv, int hd, const float* inv_freq,
-                     const int* pos, float* q_out, void* kcache, void* vcache, int S,
-                     hipStream_t st);
 int cake_swiglu_w4(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
                    const void* wu, const void* eg, const void* eu, int K, int I, void* act,
                    hipStream_t st);
 int cake_gemv_x16_w4(int dt, const void* x, const void* w, const void* e8, int K, int N,
                      float* out, int accumulate, hipStream_t st);
+// The KV writers with the cache's format as their last argument (CakeEngineOpts.kv_fmt; 0 =
+// the 16-bit entry points cake_qkv_rope* / cake_rope_kv), the prefill read and the decode
+// attention of the FP8 e4m3 KV cache
+int cake_qkv_rope_kvf(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
+                      const void* wk, const void* wv, int K, int nh, int nkv, int hd,
+                      const float* inv_freq, const int* pos, float* q_out, void* kcache,
+                      void* vcache, int S, hipStream_t st, int kv_fmt);
+int cake_qkv_rope_w8_kvf(int dt, const float* resid, const void* norm_w, float eps,
+                         const void* wq, const void* wk, const void* wv, const float* sq,
+                         const float* sk, const float* sv, int K, int nh, int nkv, int hd,
+                         const float* inv_freq, const int* pos, float* q_out, void* kcache,
+                         void* vcache, int S, hipStream_t st, int kv_fmt);
+int cake_qkv_rope_w4_kvf(int dt, const float* resid, const void* norm_w, float eps,
+                         const void* wq, const void* wk, const void* wv, const void* eq,
+                         const void* ek, const void* ev, int K, int nh, int nkv, int hd,
+                         const float* inv_freq, const int* pos, float* q_out, void* kcache,
+                         void* vcache, int S, hipStream_t st, int kv_fmt);
+int cake_rope_kv_kvf(int dt, void* q, const void* k, const void* v, int ldq, int ld, int T, int nh,
+                     int nkv, int hd, const float* inv_freq, int pos0, int S, void* kc, void* vc,
+                     hipStream_t st, int kv_fmt);
+int cake_dequant_kv_fp8(int dt, const void* k8, const void* v8, int nkv, int S, int hd, int Tk,
+                        void* k16, void* v16, hipStream_t st);
+int cake_attn_decode_kv8(int dt, const float* q, const void* kc8, const void* vc8, const int* pos,
+                         int S, int nh, int nkv, int hd, float scale, float* part,
+                         unsigned int* tickets, void* out, hipStream_t st);
 int cake_gemv_norm_f32(int dt, const float* resid, const void* norm_w, float eps, const void* w,
                        int K, int N, float* out, hipStream_t st);
 int cake_head_select(int dt, const float* resid, const void* norm_w, float eps, const void* w,
@@ -344,6 +352,10 @@ const char* const kNoQHeadTP =
     "a quantised lm_head (head_fmt 1 = fp8, 2 = mxfp4) is not supported with tensor "
     "parallelism: open the tensor-parallel engine with head_fmt 0";
 
+const char* const kNoKvTP =
+    "a quantised KV cache (kv_fmt 1 = fp8, 2 = its 16-bit oracle) is not supported with tensor "
+    "parallelism: open the tensor-parallel engine with kv_fmt 0";
+
 Json msg(const char* cmd) {
   Json j = Json::object();
   j.set("cmd", Json::string(cmd));
@@ -359,7 +371,7 @@ class Llama {
         const std::vector<int>* layers = nullptr, const CakeTPOpts* tp = nullptr,
         const CakeRemoteOpts* remote = nullptr)
       : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), hfmt_(o.head_fmt),
-        seed_(o.seed) {
+        kvfmt_(o.kv_fmt), seed_(o.seed) {
     if (dt_ != 0 && dt_ != 1) throw Error("dtype must be 0 (bf16) or 1 (f16)");
     if (wfmt_ != 0 && wfmt_ != 1 && wfmt_ != 2)
       throw Error("weight_fmt must be 0 (model dtype), 1 (fp8 e4m3 projections) or 2 (mxfp4 "
@@ -368,6 +380,21 @@ class Llama {
     if (hfmt_ != 0 && hfmt_ != 1 && hfmt_ != 2)
       throw Error("head_fmt must be 0 (model dtype), 1 (fp8 e4m3 lm_head) or 2 (mxfp4 lm_head)");
     if (hfmt_ != 0 && tp) throw Error(kNoQHeadTP);
+    if (kvfmt_ != 0 && kvfmt_ != 1 && kvfmt_ != 2)
+      throw Error("kv_fmt must be 0 (model dtype), 1 (fp8 e4m3 KV cache) or 2 (fp8 values in a "
+                  "16-bit cache: the test oracle)");
+    if (kvfmt_ != 0 && tp) throw Error(kNoKvTP);
+    if (kvfmt_ != 0) {
+      // the fp8 cache has core 2's split launch only: none of the experimental decode
+      // paths (docs/ENV.md) reads it
+      for (const char* name : {"CAKE_ATTN_OPROJ", "CAKE_ATTN_HEADS", "CAKE_MK", "CAKE_QKV_ATTN"}) {
+        const char* e = std::getenv(name);
+        if (e && *e && std::string(e) != "0")
+          throw Error(std::string("a quantised KV cache (kv_fmt ") + std::to_string(kvfmt_) +
+                      ") does not run the experimental decode path " + name + "=" + e +
+                      ": unset it or open with kv_fmt 0");
+      }
+    }
     if (init_ != 0 && init_ != 1) throw Error("init must be 0 (checkpoint) or 1 (random)");
     if (tp) {
       tp_ = tp->world;
@@ -396,6 +423,8 @@ class Llama {
     S_ = o.max_seq > 0 ? o.max_seq : 4096;
     k_ = std::max(1, o.steps_per_graph);
     if (cfg_.H % 8 || cfg_.hd % 2 || cfg_.nh % cfg_.nkv) throw Error("unsupported model shape");
+    if (kvfmt_ != 0 && cfg_.hd != 64 && cfg_.hd != 128)
+      throw Error("an fp8 KV cache needs a head dimension of 64 or 128");
     // this rank's compute shapes: the whole model, or its tensor-parallel slice
     lc_ = cfg_;
     if (tp_ > 1) {
@@ -471,7 +500,8 @@ class Llama {
     load_weights(dir);
     // one line per open: what the weights are and what they occupy
     std::fprintf(stderr,
-                 "cake engine: weights %s, lm_head %s, %lld bytes on device (rank %d, %d layers)\n",
+                 "cake engine: weights %s, lm_head %s, kv cache %s, %lld bytes on device (rank %d, "
+                 "%d layers)\n",
                  wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
                                         : "fp8 e4m3 projections (f16 rest)")
                  : wfmt_ == 2 ? (dt_ == 0 ? "mxfp4 projections (bf16 rest)"
@@ -479,6 +509,10 @@ class Llama {
                               : (dt_ == 0 ? "bf16" : "f16"),
                  !head_ ? "none" : hfmt_ == 1 ? "fp8 e4m3" : hfmt_ == 2 ? "mxfp4"
                                                 : (dt_ == 0 ? "bf16" : "f16"),
+                 kvfmt_ == 1 ? "fp8 e4m3"
+                 : kvfmt_ == 2 ? (dt_ == 0 ? "fp8 e4m3 values in bf16 (test oracle)"
+                                           : "fp8 e4m3 values in f16 (test oracle)")
+                               : (dt_ == 0 ? "bf16" : "f16"),
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
@@ -539,6 +573,7 @@ class Llama {
   const Cfg& cfg() const { return cfg_; }
   int max_seq() const { return S_; }
   int64_t weight_bytes() const { return weight_bytes_; }
+  int64_t kv_bytes() const { return 2 * (int64_t)kv_elems() * kv_esize(); }
 
   void prefill_logits(const int32_t* prompt, int T, float* host_logits) {
     hip_check(hipSetDevice(dev_), "hipSetDevice");
@@ -810,6 +845,12 @@ class Llama {
   int dt_, dev_, init_ = 0;
   int wfmt_ = 0;               // CakeEngineOpts.weight_fmt
   int hfmt_ = 0;               // CakeEngineOpts.head_fmt (0 on a rank without the head)
+  // CakeEngineOpts.kv_fmt.  1: the session caches hold one e4m3fn byte per element; decode
+  // attention is cake_attn_decode_kv8, prefill attention reads the live prefix widened into
+  // kv16_k_ / kv16_v_ (one layer's [nkv][S][hd], allocated once).  2: the 16-bit cache with
+  // fp8-valued writers (test oracle).  != 0: never the head-parallel or fused launches.
+  int kvfmt_ = 0;
+  uint16_t *kv16_k_ = nullptr, *kv16_v_ = nullptr;
   int64_t weight_bytes_ = 0;   // device weight allocations of this rank
   // head_fmt 1: head_q_ holds the e4m3 codes [V, H], head_s_ the f32 row scales; head_fmt 2:
   // head_q_ the packed e2m1 codes [V, H/2], head_e_ the e8m0 bytes [V, H/32].  lm_head_ is
@@ -896,7 +937,7 @@ class Llama {
   std::vector<void*> allocs_;
   void *embed_ = nullptr, *norm_ = nullptr, *lm_head_ = nullptr;
   std::vector<LayerW> layers_;
-  struct KV { uint16_t *k, *v; };           // [local layers][nkv][S][hd]
+  struct KV { uint8_t *k, *v; };            // [local layers][nkv][S][hd], kv_esize() bytes each
   std::map<uint64_t, KV> kv_;
   std::list<uint64_t> lru_;
   KV cur_{nullptr, nullptr};
@@ -1192,6 +1233,13 @@ class Llama {
   void alloc_state() {
     const Cfg& c = lc_;
     kv_session(0);  // session 0: generation / pipeline
+    if (kvfmt_ == 1) {  // prefill's 16-bit view of one layer's live prefix
+      const size_t n = (size_t)c.nkv * S_ * c.hd;
+      kv16_k_ = dalloc<uint16_t>(n);
+      kv16_v_ = dalloc<uint16_t>(n);
+      hip_check(hipMemset(kv16_k_, 0, n * 2), "memset");
+      hip_check(hipMemset(kv16_v_, 0, n * 2), "memset");
+    }
     const std::vector<float> f = c.inv_freq();
     inv_freq_ = dalloc<float>(f.size());
     hip_check(hipMemcpy(inv_freq_, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice),
@@ -1228,11 +1276,11 @@ class Llama {
     {
       const char* e = std::getenv("CAKE_ATTN_OPROJ");
       // (reads o_proj as 16-bit rows: off with fp8 and mxfp4 weights)
-      if (e && std::string(e) == "1" && wfmt_ == 0) ao_ = ao_fns();
+      if (e && std::string(e) == "1" && wfmt_ == 0 && kvfmt_ == 0) ao_ = ao_fns();
       ao_ok_ = ao_.run != nullptr && ao_.supported(c.nh, c.nkv, c.hd, c.H) != 0;
     }
     // CAKE_ATTN_HEADS=<max keys>[:<waves>]: the head-parallel short-context attention
-    if (!ao_ok_) {
+    if (!ao_ok_ && kvfmt_ == 0) {
       const char* e = std::getenv("CAKE_ATTN_HEADS");
       int mx = 0, nw = 2, pfd = 2;
       if (e && *e) std::sscanf(e, "%d:%d:%d", &mx, &nw, &pfd);
@@ -1262,8 +1310,10 @@ class Llama {
     hip_check(hipDeviceSynchronize(), "sync");  // null-stream memsets before st_ work
   }
 
-  uint16_t* kc(int l) const { return cur_.k + (size_t)l * lc_.nkv * S_ * lc_.hd; }
-  uint16_t* vc(int l) const { return cur_.v + (size_t)l * lc_.nkv * S_ * lc_.hd; }
+  size_t kv_esize() const { return kvfmt_ == 1 ? 1 : 2; }  // bytes per cache element
+  size_t kv_elems() const { return owned_.size() * (size_t)lc_.nkv * S_ * lc_.hd; }  // of K
+  void* kc(int l) const { return cur_.k + (size_t)l * lc_.nkv * S_ * lc_.hd * kv_esize(); }
+  void* vc(int l) const { return cur_.v + (size_t)l * lc_.nkv * S_ * lc_.hd * kv_esize(); }
 
   // KV cache of one session (a master connection of a TCP worker; 0 = generation):
   // allocated on first use, least recently used dropped past kMaxSessions (P4)
@@ -1277,8 +1327,8 @@ class Llama {
           if (x != 0) { victim = x; break; }
         drop_session(victim);
       }
-      const size_t n = owned_.size() * (size_t)lc_.nkv * S_ * lc_.hd;
-      KV kv{dalloc<uint16_t>(n), dalloc<uint16_t>(n)};
+      const size_t n = kv_elems() * kv_esize();
+      KV kv{dalloc<uint8_t>(n), dalloc<uint8_t>(n)};
       it = kv_.emplace(id, kv).first;
     }
     lru_.remove(id);
@@ -1525,15 +1575,26 @@ class Llama {
       gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, w.eqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr,
            0, T, nqkv, c.H, "gemm qkv");
       uint16_t* q = reinterpret_cast<uint16_t*>(qkv_);
-      k_check(cake_rope_kv(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
-                           inv_freq_, pos0, S_, kc(l), vc(l), st_), "rope_kv");
+      // (kv_fmt 0: cake_rope_kv itself)
+      k_check(cake_rope_kv_kvf(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
+                               inv_freq_, pos0, S_, kc(l), vc(l), st_, kvfmt_), "rope_kv");
+      const void *kr = kc(l), *vr = vc(l);  // what the attention reads
+      if (kvfmt_ == 1) {
+        // the live prefix, the rows just written included, widened into the 16-bit scratch:
+        // one extra pass over it per layer per prefill call (stream order keeps the layers'
+        // uses of the scratch apart)
+        k_check(cake_dequant_kv_fp8(dt_, kc(l), vc(l), c.nkv, S_, c.hd, Tk, kv16_k_, kv16_v_,
+                                    st_), "dequant_kv_fp8");
+        kr = kv16_k_;
+        vr = kv16_v_;
+      }
       // [B, H, rows, D] strides of q (a column block of qkv), the layer's cache, the output
       const long long Sh = (long long)S_ * c.hd;
       const long long strides[12] = {(long long)T * nqkv, c.hd, nqkv,
                                      (long long)c.nkv * Sh, Sh, c.hd,
                                      (long long)c.nkv * Sh, Sh, c.hd,
                                      (long long)T * nq, c.hd, nq};
-      k_check(cake_flash_attn(dt_, q, kc(l), vc(l), att_, 1, c.nh, c.nkv, T, Tk, c.hd, strides,
+      k_check(cake_flash_attn(dt_, q, kr, vr, att_, 1, c.nh, c.nkv, T, Tk, c.hd, strides,
                               scale(), 1, pos0, st_), "flash_attn");
       if (tp_ > 1) {  // partial o_proj over this rank's heads, summed over the ranks
         gemm(kEpiStore32, att_, nq, w.wo, nq, nullptr, 0, ppart_, c.H, T, c.H, nq, "gemm o");
@@ -1668,6 +1729,13 @@ class Llama {
 
  private:
 
+  // decode attention of local layer l over the fp8 code cache (kv_fmt 1)
+  void attn_kv8(int l) {
+    const Cfg& c = lc_;
+    k_check(cake_attn_decode_kv8(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
+                                 part_, tickets_, attn_out_, st_), "attn_decode_kv8");
+  }
+
   void step_layers(const std::vector<int>* sel = nullptr) {
     const Cfg& c = lc_;
     const int nq = c.nh * c.hd, nk = c.nkv * c.hd;
@@ -1678,11 +1746,14 @@ class Llama {
       if (wfmt_ == 2) {  // mxfp4 projections: the _w4 twins of the four GEMVs (tp_ == 1)
         const uint8_t* q4 = reinterpret_cast<const uint8_t*>(w.wqkv);
         const size_t rb = (size_t)c.H / 2, re = (size_t)c.H / 32;  // bytes per q|k|v row
-        k_check(cake_qkv_rope_w4(dt_, resid_, w.ln1, (float)c.eps, q4, q4 + (size_t)nq * rb,
-                                 q4 + (size_t)(nq + nk) * rb, w.eqkv, w.eqkv + (size_t)nq * re,
-                                 w.eqkv + (size_t)(nq + nk) * re, c.H, c.nh, c.nkv, c.hd,
-                                 inv_freq_, pos_, q_, kc(l), vc(l), S_, st_), "qkv_rope_w4");
-        if (short_step_)  // head-parallel short-context attention
+        k_check(cake_qkv_rope_w4_kvf(dt_, resid_, w.ln1, (float)c.eps, q4, q4 + (size_t)nq * rb,
+                                     q4 + (size_t)(nq + nk) * rb, w.eqkv, w.eqkv + (size_t)nq * re,
+                                     w.eqkv + (size_t)(nq + nk) * re, c.H, c.nh, c.nkv, c.hd,
+                                     inv_freq_, pos_, q_, kc(l), vc(l), S_, st_, kvfmt_),
+                "qkv_rope_w4");
+        if (kvfmt_ == 1)
+          attn_kv8(l);
+        else if (short_step_)  // head-parallel short-context attention
           k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
                                          scale(), attn_out_, st_), "attn_heads");
         else
@@ -1697,11 +1768,13 @@ class Llama {
       }
       if (wfmt_ == 1) {  // fp8 projections: the _w8 twins of the four GEMVs (tp_ == 1)
         const uint8_t* q8 = reinterpret_cast<const uint8_t*>(w.wqkv);
-        k_check(cake_qkv_rope_w8(dt_, resid_, w.ln1, (float)c.eps, q8, q8 + (size_t)nq * c.H,
-                                 q8 + (size_t)(nq + nk) * c.H, w.sqkv, w.sqkv + nq,
-                                 w.sqkv + nq + nk, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
-                                 kc(l), vc(l), S_, st_), "qkv_rope_w8");
-        if (short_step_)  // head-parallel short-context attention
+        k_check(cake_qkv_rope_w8_kvf(dt_, resid_, w.ln1, (float)c.eps, q8, q8 + (size_t)nq * c.H,
+                                     q8 + (size_t)(nq + nk) * c.H, w.sqkv, w.sqkv + nq,
+                                     w.sqkv + nq + nk, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
+                                     kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope_w8");
+        if (kvfmt_ == 1)
+          attn_kv8(l);
+        else if (short_step_)  // head-parallel short-context attention
           k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
                                          scale(), attn_out_, st_), "attn_heads");
         else
@@ -1715,10 +1788,13 @@ class Llama {
         continue;
       }
       const uint16_t* wqkv = reinterpret_cast<const uint16_t*>(w.wqkv);
-      k_check(cake_qkv_rope(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
-                            wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
-                            pos_, q_, kc(l), vc(l), S_, st_), "qkv_rope");
-      if (short_step_ && ao_ok_) {  // one split: attention + o_proj in one launch
+      k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
+                                wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
+                                pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
+      if (kvfmt_ == 1) {  // fp8 cache: core 2's split launch over the codes (tp_ == 1)
+        attn_kv8(l);
+        k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, resid_, 1, st_), "o_proj");
+      } else if (short_step_ && ao_ok_) {  // one split: attention + o_proj in one launch
         k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.wo,
                                 nq, c.H, tp_ > 1 ? partial_ : resid_, tp_ > 1 ? 0 : 1, ao_ws_,
                                 ao_tickets_, tickets_ + 2 * c.nkv, st_), "attn_oproj");
@@ -2901,6 +2977,7 @@ CAKE_API void* cake_engine_open_tp(const char* model_dir, const CakeEngineOpts* 
     if (!model_dir || !opts || !tp) throw cake::Error("null argument");
     if (opts->weight_fmt != 0) throw cake::Error(cake::kNoFp8TP);
     if (opts->head_fmt != 0) throw cake::Error(cake::kNoQHeadTP);
+    if (opts->kv_fmt != 0) throw cake::Error(cake::kNoKvTP);
     return new Llama(model_dir, *opts, nullptr, nullptr, tp);
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());
@@ -2937,6 +3014,10 @@ CAKE_API int32_t cake_engine_info(void* h, int32_t* o) {
   const int32_t v[8] = {c.V, c.H, c.L, c.nh, c.nkv, c.hd, c.I, m->max_seq()};
   std::memcpy(o, v, sizeof(v));
   return 0;
+}
+
+CAKE_API int64_t cake_engine_kv_bytes(void* h) {
+  return h ? static_cast<Llama*>(h)->kv_bytes() : 0;
 }
 
 CAKE_API int64_t cake_engine_weight_bytes(void* h) {

@@ -36,6 +36,16 @@ struct CakeEngineOpts {
                             // projections' row quantisers.  The embedding stays 16-bit (tied:
                             // the quantised head is an extra allocation).  Ranks and workers
                             // without the head ignore it.  1, 2: not with open_tp.
+  int32_t kv_fmt;           // 0: KV cache in the model dtype; 1: FP8 e4m3fn KV cache, one code
+                            // per element and no scale (code = rne_e4m3(clamp(x, -448, 448)) of
+                            // the f32 value the writer holds), half the bytes; every attention
+                            // read, prefill included, sees the quantised values.  2: the test
+                            // oracle of 1 only — the 16-bit cache and its readers, every writer
+                            // storing the code's value (exact in bf16 and f16); it saves no
+                            // memory and an engine opened with 1 must equal it bit for bit.
+                            // Chosen independently of weight_fmt / head_fmt; each pipeline
+                            // rank's or worker's own value governs its own caches.  1, 2: not
+                            // with open_tp, not with the experimental decode launches.
 };
 
 // Layer-sharded pipeline over one process per GPU.  Placement: `owners[l]` is the rank
@@ -135,6 +145,9 @@ int32_t cake_engine_eos(void* engine, int32_t* out, int32_t cap);
 // projections and their scales (weight_fmt 1: f32 per row; 2: one byte per 32 elements),
 // the quantised head and its scales (head_fmt 1, 2: also when the embeddings are tied)
 int64_t cake_engine_weight_bytes(void* engine);
+// bytes of one session's K + V cache allocation on this rank:
+// 2 * local layers * nkv * max_seq * hd * (kv_fmt 1 ? 1 : 2)
+int64_t cake_engine_kv_bytes(void* engine);
 // Prefill `prompt` from position 0, then generate up to max_new tokens (the first comes
 // from the prefill logits), stopping after an EOS id.  Tokens go to out[] (and cb).
 // Returns 0 or an error code (message in err).

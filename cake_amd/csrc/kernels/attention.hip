@@ -64,6 +64,17 @@ __global__ __launch_bounds__(AttnGeom2<NREP>::NT) void attn2_decode_kernel(AttnD
                                                                     lds, gridDim.x);
 }
 
+// Core 2 over an FP8 e4m3 KV cache (a.kc / a.vc: one code per element): the same block
+// walk, split policy and merges; only the K / V loads and their widening differ
+// (attn_core2.h, KV8).
+template <int DT, int HD, int NREP, int PFD>
+__global__ __launch_bounds__(AttnGeom2<NREP>::NT) void attn2_decode_kv8_kernel(AttnDecArgs a) {
+  __shared__ __attribute__((aligned(16)))
+      float lds[attn2_smem_floats<HD, NREP, AttnGeom2<NREP>::NW>()];
+  attn2_decode_block<DT, HD, NREP, false, AttnGeom2<NREP>::NW, PFD, NoHook, false, true>(
+      a, blockIdx.x, blockIdx.y, lds, gridDim.x);
+}
+
 // Head-parallel short-context decode: one workgroup per QUERY head (grid nh), NW waves
 // over the key blocks, the whole context as one split.  Against the per-kv-head launch
 // (nkv workgroups, each carrying its group's nrep heads) the same keys are read nrep
@@ -270,6 +281,55 @@ CAKE_API int cake_attn_decode(int dt, const float* q, const void* kc, const void
                       g_attn_min_keys, splits, g_attn_stamps, g_attn_target,
                       g_attn_single, g_attn_drop_partials};
   DISPATCH_DT_HD(dt, hd, return (launch_decode<DT, HD>(nh / nkv, grid, st, a)));
+  return (int)hipErrorInvalidValue;
+}
+
+// ---- decode over an FP8 e4m3 KV cache (core 2 only)
+template <int DT, int HD>
+static int launch_decode_kv8(int n_rep, dim3 grid, hipStream_t st, const AttnDecArgs& a) {
+  // the split cap, prefetch depth and residency trim of launch_decode; where that would
+  // run core 1 (no split per kv head resident) there is no fp8 twin: an error
+#define CAKE_DEC8(NR, PF)                                                                       \
+  do {                                                                                          \
+    const int fit = resident_splits(attn2_decode_kv8_kernel<DT, HD, NR, PF>, AttnGeom2<NR>::NT, \
+                                    (int)grid.x, (int)grid.y);                                  \
+    if (fit == 0) return (int)hipErrorInvalidValue;                                             \
+    AttnDecArgs a2 = a;                                                                         \
+    a2.maxsplit = fit;                                                                          \
+    hipLaunchKernelGGL((attn2_decode_kv8_kernel<DT, HD, NR, PF>), dim3(grid.x, fit),            \
+                       dim3(AttnGeom2<NR>::NT), 0, st, a2);                                     \
+  } while (0)
+#define CAKE_DEC(NR)                                                                            \
+  if (g_attn_prefetch == 2 || (g_attn_prefetch == 0 && grid.y > 8)) CAKE_DEC8(NR, 2);           \
+  else CAKE_DEC8(NR, 1)
+  switch (n_rep) {
+    case 1: CAKE_DEC(1); break;
+    case 2: CAKE_DEC(2); break;
+    case 4: CAKE_DEC(4); break;
+    case 8: CAKE_DEC(8); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef CAKE_DEC
+#undef CAKE_DEC8
+  return (int)hipGetLastError();
+}
+
+// cake_attn_decode over code caches kc8 / vc8 [nkv][S][hd] (one e4m3fn byte per element,
+// written by the *_kvf entry points with kv_fmt 1).  Core 2 only: hipErrorInvalidValue
+// under cake_attn_set_impl(1).
+CAKE_API int cake_attn_decode_kv8(int dt, const float* q, const void* kc8, const void* vc8,
+                                  const int* pos, int S, int nh, int nkv, int hd, float scale,
+                                  float* part, unsigned int* tickets, void* out,
+                                  hipStream_t st) {
+  if (nkv <= 0 || nh % nkv || S <= 0 || g_attn_impl != 2) return (int)hipErrorInvalidValue;
+  const int ms = attn_max_split(S);
+  const int splits = g_attn_split_cap > 0 && g_attn_split_cap < ms ? g_attn_split_cap : ms;
+  const dim3 grid(nkv, splits);
+  const AttnDecArgs a{q, (const uint16_t*)kc8, (const uint16_t*)vc8, pos, S,
+                      scale * 1.4426950408889634f, part, tickets, (uint16_t*)out,
+                      g_attn_min_keys, splits, g_attn_stamps, g_attn_target,
+                      g_attn_single, g_attn_drop_partials};
+  DISPATCH_DT_HD(dt, hd, return (launch_decode_kv8<DT, HD>(nh / nkv, grid, st, a)));
   return (int)hipErrorInvalidValue;
 }
 

@@ -114,12 +114,18 @@ struct NoHook {
 // front of them (attn_oproj.hip: the o_proj weight tile)
 // ONE: the head-parallel short-context launch (attn_head_kernel): one split, plain loads,
 // no epoch word (tickets untouched); g is then a QUERY head (NREP 1) and kvh its kv head.
+// KV8: a.kc / a.vc hold one e4m3fn code per element (FP8 KV cache, same [nkv][S][hd]
+// layout).  The lane-to-element mapping is the 16-bit one with 8-byte loads where that has
+// 16-byte ones: a K fragment is widened exactly to 8 values of DT in front of the same
+// MFMA, a V fragment exactly to f32, so the output equals, bit for bit, the 16-bit kernel's
+// on a cache holding the codes' values.
 template <int DT, int HD, int NREP, bool FUSED = false, int NW = AttnGeom2<NREP>::NW,
-          int PFD = 2, class Hook = NoHook, bool ONE = false>
+          int PFD = 2, class Hook = NoHook, bool ONE = false, bool KV8 = false>
 __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, int s,
                                                    float* lds, int ng, const Hook& hook = Hook(),
                                                    int kvh = -1) {
   static_assert(PFD == 1 || PFD == 2 || PFD == 4, "prefetch depth 1, 2 or 4");
+  static_assert(!(KV8 && (FUSED || ONE)), "the fp8 cache runs the plain split launch only");
   constexpr int DS = HD / 32;    // MFMA k-steps (A fragments) per key block
   constexpr int NCH = HD / 8;    // 8-dim chunks per row
   constexpr int KPL = NCH / 4;   // keys per lane in P.V (16 keys over 64 / NCH key groups)
@@ -134,12 +140,14 @@ __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, 
   unsigned long long stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   ATTN_STAMP(0);
   const int kv = kvh < 0 ? g : kvh;
-  const uint16_t* kgp = a.kc + (size_t)kv * a.S * HD;
-  const uint16_t* vgp = a.vc + (size_t)kv * a.S * HD;
+  using KvT = std::conditional_t<KV8, uint8_t, uint16_t>;  // cache element
+  using KvV = std::conditional_t<KV8, uint2, uint4>;        // 8 of them: one load
+  const KvT* kgp = reinterpret_cast<const KvT*>(a.kc) + (size_t)kv * a.S * HD;
+  const KvT* vgp = reinterpret_cast<const KvT*>(a.vc) + (size_t)kv * a.S * HD;
 
   // one block's operands: K A-fragments and V rows of this lane
   // PFD slots of one block's operands (slot index a compile-time constant everywhere)
-  uint4 kf[PFD][DS], vf[PFD][KPL];
+  KvV kf[PFD][DS], vf[PFD][KPL];
   __amdgpu_buffer_rsrc_t krs, vrs;
   if constexpr (FUSED) { krs = sc1_rsrc(kgp); vrs = sc1_rsrc(vgp); }
   using I0 = std::integral_constant<int, 0>;
@@ -151,14 +159,14 @@ __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, 
       const int r = min(key0 + col, last);
       const size_t o = (size_t)r * HD + d * 32 + rg * 8;
       if constexpr (FUSED) kf[SL][d] = ld16_sc1(krs, o * 2);
-      else kf[SL][d] = *reinterpret_cast<const uint4*>(kgp + o);
+      else kf[SL][d] = *reinterpret_cast<const KvV*>(kgp + o);
     }
 #pragma unroll
     for (int j = 0; j < KPL; ++j) {
       const int r = min(key0 + kg * KPL + j, last);
       const size_t o = (size_t)r * HD + ch * 8;
       if constexpr (FUSED) vf[SL][j] = ld16_sc1(vrs, o * 2);
-      else vf[SL][j] = *reinterpret_cast<const uint4*>(vgp + o);
+      else vf[SL][j] = *reinterpret_cast<const KvV*>(vgp + o);
     }
   };
 
@@ -257,7 +265,7 @@ __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, 
   auto block = [&](auto slot, int b) {
     constexpr int SL = decltype(slot)::value;
     const int key0 = kb + b * kBlk;
-    uint4 kc[DS], vc[KPL];
+    KvV kc[DS], vc[KPL];
 #pragma unroll
     for (int d = 0; d < DS; ++d) kc[d] = kf[SL][d];
 #pragma unroll
@@ -266,7 +274,10 @@ __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, 
     // scores: S[key 4 rg + e][col]
     cf32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int d = 0; d < DS; ++d) acc = cmfma<DT>(kc[d], qf[d], acc);
+    for (int d = 0; d < DS; ++d) {
+      if constexpr (KV8) acc = cmfma<DT>(kv_widen8<DT>(kc[d]), qf[d], acc);
+      else acc = cmfma<DT>(kc[d], qf[d], acc);
+    }
     float sc[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) sc[e] = key0 + 4 * rg + e < ke ? acc[e] : -INFINITY;
@@ -298,7 +309,8 @@ __device__ __forceinline__ void attn2_decode_block(const AttnDecArgs& a, int g, 
     for (int j = 0; j < KPL; ++j) {
       const int key = key0 + kg * KPL + j;
       float vv[8];
-      unpack8<DT>(vc[j], vv);
+      if constexpr (KV8) kv_unpack8(vc[j], vv);
+      else unpack8<DT>(vc[j], vv);
       if (key >= ke) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) vv[e] = 0.f;

@@ -64,6 +64,71 @@ __device__ __forceinline__ void unpack8(const uint4 v, float* o) {
   }
 }
 
+// ---- FP8 KV cache (CakeEngineOpts.kv_fmt; oracle: ops/reference.py quant_kv_fp8)
+// kv_fmt 0: 16-bit cache; 1: one OCP e4m3fn code per element, no scale; 2: the code's
+// value kept in a 16-bit cache (exact in bf16 and f16: the test oracle of format 1).
+enum KvFmt : int { kKv16 = 0, kKvFp8 = 1, kKvFp8Emu = 2 };
+
+// two f32 -> two e4m3fn codes (bits 0-7: a, 8-15: b): one v_cvt_pk_fp8_f32 (RNE) after an
+// explicit clamp to +-448, so a finite input never gives the NaN code whatever the
+// conversion's overflow mode
+__device__ __forceinline__ uint32_t kv_codes2(float a, float b) {
+  a = fminf(fmaxf(a, -448.f), 448.f);
+  b = fminf(fmaxf(b, -448.f), 448.f);
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
+}
+
+// 8 f32 -> 8 codes (one 8-byte store)
+__device__ __forceinline__ uint2 kv_codes8(const float* f) {
+  return make_uint2(kv_codes2(f[0], f[1]) | (kv_codes2(f[2], f[3]) << 16),
+                    kv_codes2(f[4], f[5]) | (kv_codes2(f[6], f[7]) << 16));
+}
+
+// 8 codes -> f32 (v_cvt_pk_f32_fp8: exact)
+__device__ __forceinline__ void kv_unpack8(const uint2 v, float* o) {
+  const uint32_t w[2] = {v.x, v.y};
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true);
+    o[4 * i] = lo[0]; o[4 * i + 1] = lo[1]; o[4 * i + 2] = hi[0]; o[4 * i + 3] = hi[1];
+  }
+}
+
+// 8 codes -> 8 16-bit values (exact: every e4m3 value is a bf16 and an f16 value)
+template <int DT>
+__device__ __forceinline__ uint4 kv_widen8(const uint2 v) {
+  float f[8];
+  kv_unpack8(v, f);
+  uint32_t o[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    o[i] = (uint32_t)from_f32<DT>(f[2 * i]) | ((uint32_t)from_f32<DT>(f[2 * i + 1]) << 16);
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// The decode QKV epilogues' store of one rotated pair (elements off and off + half of the
+// layer's cache) in the cache's format; kv_fmt is a kernel argument (wave-uniform branch).
+template <int DT>
+__device__ __forceinline__ void kv_store_pair(uint16_t* cache, size_t off, int half, float oa,
+                                              float ob, int kv_fmt) {
+  if (kv_fmt == kKv16) {
+    cache[off] = from_f32<DT>(oa);
+    cache[off + half] = from_f32<DT>(ob);
+    return;
+  }
+  const uint32_t c2 = kv_codes2(oa, ob);
+  if (kv_fmt == kKvFp8) {
+    uint8_t* c8 = reinterpret_cast<uint8_t*>(cache);
+    c8[off] = (uint8_t)(c2 & 0xffu);
+    c8[off + half] = (uint8_t)(c2 >> 8);
+  } else {
+    const auto f = __builtin_amdgcn_cvt_pk_f32_fp8((int)c2, false);
+    cache[off] = from_f32<DT>(f[0]);
+    cache[off + half] = from_f32<DT>(f[1]);
+  }
+}
+
 // Wave-wide butterfly reductions without LDS: DPP (quad_perm xor 1 / xor 2,
 // row_half_mirror, row_mirror) inside each 16-lane row, then the gfx950 lane-swap
 // instructions across rows (v_permlane16_swap: rows 0|1 and 2|3; v_permlane32_swap:

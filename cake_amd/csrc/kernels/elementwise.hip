@@ -182,6 +182,128 @@ __global__ __launch_bounds__(256) void rope_kv_vec_kernel(
   }
 }
 
+// ---- FP8 e4m3 KV cache: the prefill writers and the prefill read (common.h KvFmt)
+// Twins of rope_kv_kernel / rope_kv_vec_kernel for KVF = kKvFp8 (kc / vc hold one code per
+// element) and kKvFp8Emu (16-bit cache holding the codes' values).  q is roped in place in
+// 16 bits as before; K's code comes from the f32 rotation (no 16-bit rounding in between),
+// V's from its 16-bit GEMM output widened to f32.
+template <int DT, int KVF>
+__global__ void rope_kv_q8_kernel(uint16_t* __restrict__ q, const uint16_t* __restrict__ k,
+                                  const uint16_t* __restrict__ v, int ldq, int ld, int nh,
+                                  int nkv, int hd, const float* __restrict__ inv_freq, int pos0,
+                                  int S, uint16_t* __restrict__ kc, uint16_t* __restrict__ vc) {
+  // K's codes are defined on the f32 rotation with every product and sum rounded on its
+  // own (the oracle's arithmetic), so no fused multiply-add in this kernel; q takes the
+  // same rotation (a 16-bit q may differ from rope_kv_kernel's in its last bit)
+#pragma clang fp contract(off)
+  const int t = blockIdx.x, pos = pos0 + t, half = hd >> 1;
+  const int nq = nh * half, nk = nkv * half;
+  for (int p = threadIdx.x; p < nq + 2 * nk; p += blockDim.x) {
+    if (p < nq + nk) {
+      const bool isq = p < nq;
+      const int pp = isq ? p : p - nq;
+      const int head = pp / half, i = pp - head * half;
+      float s, c;
+      sincosf((float)pos * inv_freq[i], &s, &c);
+      const uint16_t* src = isq ? q + (size_t)t * ldq : k + (size_t)t * ld;
+      const float a = to_f32<DT>(src[head * hd + i]);
+      const float b = to_f32<DT>(src[head * hd + i + half]);
+      const float oa = a * c - b * s, ob = a * s + b * c;
+      if (isq) {
+        q[(size_t)t * ldq + head * hd + i] = from_f32<DT>(oa);
+        q[(size_t)t * ldq + head * hd + i + half] = from_f32<DT>(ob);
+      } else {
+        kv_store_pair<DT>(kc, ((size_t)head * S + pos) * hd + i, half, oa, ob, KVF);
+      }
+    } else {
+      const int pp = p - nq - nk;
+      const int head = pp / half, i = pp - head * half;
+      const uint16_t* src = v + (size_t)t * ld + head * hd;
+      kv_store_pair<DT>(vc, ((size_t)head * S + pos) * hd + i, half, to_f32<DT>(src[i]),
+                        to_f32<DT>(src[i + half]), KVF);
+    }
+  }
+}
+
+// 8 f32 -> the cache's 8 elements at element offset off: one 8-byte store of codes, or one
+// 16-byte store of their values
+template <int DT, int KVF>
+__device__ __forceinline__ void kv_store8(uint16_t* cache, size_t off, const float* f) {
+  const uint2 codes = kv_codes8(f);
+  if constexpr (KVF == kKvFp8)
+    *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(cache) + off) = codes;
+  else
+    *reinterpret_cast<uint4*>(cache + off) = kv_widen8<DT>(codes);
+}
+
+template <int DT, int KVF>
+__global__ __launch_bounds__(256) void rope_kv_vec_q8_kernel(
+    uint16_t* __restrict__ q, const uint16_t* __restrict__ k, const uint16_t* __restrict__ v,
+    int ldq, int ld, int nh, int nkv, int hd, const float* __restrict__ inv_freq, int pos0, int S,
+    uint16_t* __restrict__ kc, uint16_t* __restrict__ vc) {
+#pragma clang fp contract(off)  // see rope_kv_q8_kernel
+  const int t = blockIdx.x, pos = pos0 + t, half = hd >> 1, hv = half >> 3;
+  const int nrope = (nh + nkv) * hv, nv = nkv * (hd >> 3);
+  __shared__ float s_sn[128], s_cs[128];
+  for (int i = threadIdx.x; i < half; i += blockDim.x) sincosf((float)pos * inv_freq[i], &s_sn[i], &s_cs[i]);
+  __syncthreads();
+  for (int p = threadIdx.x; p < nrope + nv; p += blockDim.x) {
+    if (p < nrope) {
+      const int head = p / hv, i0 = (p - head * hv) * 8;
+      const bool isq = head < nh;
+      const int hh = isq ? head : head - nh;
+      const uint16_t* src = isq ? q + (size_t)t * ldq + hh * hd : k + (size_t)t * ld + hh * hd;
+      float a[8], b[8], oa[8], ob[8];
+      unpack8<DT>(*reinterpret_cast<const uint4*>(src + i0), a);
+      unpack8<DT>(*reinterpret_cast<const uint4*>(src + i0 + half), b);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float sn = s_sn[i0 + e], cs = s_cs[i0 + e];
+        oa[e] = a[e] * cs - b[e] * sn;
+        ob[e] = a[e] * sn + b[e] * cs;
+      }
+      if (isq) {
+        uint16_t ha[8], hb[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { ha[e] = from_f32<DT>(oa[e]); hb[e] = from_f32<DT>(ob[e]); }
+        uint16_t* dst = q + (size_t)t * ldq + hh * hd;
+        *reinterpret_cast<uint4*>(dst + i0) = *reinterpret_cast<const uint4*>(ha);
+        *reinterpret_cast<uint4*>(dst + i0 + half) = *reinterpret_cast<const uint4*>(hb);
+      } else {
+        const size_t row = ((size_t)hh * S + pos) * hd;
+        kv_store8<DT, KVF>(kc, row + i0, oa);
+        kv_store8<DT, KVF>(kc, row + i0 + half, ob);
+      }
+    } else {
+      const int pp = p - nrope, per = hd >> 3;
+      const int head = pp / per, c = (pp - head * per) * 8;
+      float f[8];
+      unpack8<DT>(*reinterpret_cast<const uint4*>(v + (size_t)t * ld + head * hd + c), f);
+      kv_store8<DT, KVF>(vc, ((size_t)head * S + pos) * hd + c, f);
+    }
+  }
+}
+
+// Prefill read: rows [0, Tk) of every kv head of the code caches k8 / v8 [nkv][S][hd]
+// widened (exactly) into 16-bit scratches of the same layout, which the flash kernel then
+// reads with the cache's own strides.  One thread per 16 codes; blockIdx.y: 0 = K, 1 = V.
+template <int DT>
+__global__ __launch_bounds__(256) void dequant_kv_fp8_kernel(
+    const uint8_t* __restrict__ k8, const uint8_t* __restrict__ v8, int nkv, int S, int hd, int Tk,
+    uint16_t* __restrict__ k16, uint16_t* __restrict__ v16) {
+  const uint8_t* src = blockIdx.y == 0 ? k8 : v8;
+  uint16_t* dst = blockIdx.y == 0 ? k16 : v16;
+  const size_t per_head = (size_t)Tk * hd / 16, n = per_head * nkv;
+  for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < n;
+       c += (size_t)gridDim.x * blockDim.x) {
+    const size_t head = c / per_head;
+    const size_t e = head * S * hd + (c - head * per_head) * 16;
+    const uint4 w = *reinterpret_cast<const uint4*>(src + e);
+    *reinterpret_cast<uint4*>(dst + e) = kv_widen8<DT>(make_uint2(w.x, w.y));
+    *reinterpret_cast<uint4*>(dst + e + 8) = kv_widen8<DT>(make_uint2(w.z, w.w));
+  }
+}
+
 // act = silu(g) * u   (16-bit in/out), gu = [T, 2, I] packed or separate.
 template <int DT>
 __global__ void silu_mul_kernel(const uint16_t* __restrict__ g, const uint16_t* __restrict__ u,
@@ -448,6 +570,46 @@ CAKE_API int cake_rope_kv(int dt, void* q, const void* k, const void* v, int ldq
                                      (uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, ldq, ld, nh,
                                      nkv, hd, inv_freq, pos0, S, (uint16_t*)kc,
                                      (uint16_t*)vc));
+  return (int)hipGetLastError();
+}
+
+// cake_rope_kv with the cache's format (common.h KvFmt): 0 = cake_rope_kv itself; 1 = kc / vc
+// are code caches (one e4m3fn byte per element); 2 = 16-bit caches that receive the codes'
+// values.  hd % 16 == 0 for 1 and 2.
+CAKE_API int cake_rope_kv_kvf(int dt, void* q, const void* k, const void* v, int ldq, int ld, int T,
+                              int nh, int nkv, int hd, const float* inv_freq, int pos0, int S,
+                              void* kc, void* vc, hipStream_t st, int kv_fmt) {
+  if (kv_fmt == kKv16)
+    return cake_rope_kv(dt, q, k, v, ldq, ld, T, nh, nkv, hd, inv_freq, pos0, S, kc, vc, st);
+  if ((kv_fmt != kKvFp8 && kv_fmt != kKvFp8Emu) || hd % 16 || T < 1 || pos0 < 0 ||
+      (long long)pos0 + T > S)
+    return (int)hipErrorInvalidValue;
+  const bool vec = hd <= 256 && ldq % 8 == 0 && ld % 8 == 0 &&
+                   ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)kc | (uintptr_t)vc) % 16 == 0;
+#define CAKE_ROPE_Q8(KERN, KVF)                                                                  \
+  DISPATCH_DT(dt, hipLaunchKernelGGL((KERN<DT, KVF>), dim3(T), dim3(256), 0, st, (uint16_t*)q,   \
+                                     (const uint16_t*)k, (const uint16_t*)v, ldq, ld, nh, nkv,   \
+                                     hd, inv_freq, pos0, S, (uint16_t*)kc, (uint16_t*)vc))
+  if (vec && kv_fmt == kKvFp8) CAKE_ROPE_Q8(rope_kv_vec_q8_kernel, kKvFp8);
+  else if (vec) CAKE_ROPE_Q8(rope_kv_vec_q8_kernel, kKvFp8Emu);
+  else if (kv_fmt == kKvFp8) CAKE_ROPE_Q8(rope_kv_q8_kernel, kKvFp8);
+  else CAKE_ROPE_Q8(rope_kv_q8_kernel, kKvFp8Emu);
+#undef CAKE_ROPE_Q8
+  return (int)hipGetLastError();
+}
+
+// k16 / v16 rows [0, Tk) of every kv head = the values of the codes in k8 / v8 (all four
+// [nkv][S][hd], 16-byte aligned); rows >= Tk of the scratches are not touched
+CAKE_API int cake_dequant_kv_fp8(int dt, const void* k8, const void* v8, int nkv, int S, int hd,
+                                 int Tk, void* k16, void* v16, hipStream_t st) {
+  if (nkv < 1 || hd < 16 || hd % 16 || Tk < 1 || Tk > S ||
+      ((uintptr_t)k8 | (uintptr_t)v8 | (uintptr_t)k16 | (uintptr_t)v16) % 16)
+    return (int)hipErrorInvalidValue;
+  const size_t n = (size_t)nkv * Tk * hd / 16, want = (n + 255) / 256;
+  const dim3 grid((unsigned)(want < 4096 ? want : 4096), 2);
+  DISPATCH_DT(dt, hipLaunchKernelGGL((dequant_kv_fp8_kernel<DT>), grid, dim3(256), 0, st,
+                                     (const uint8_t*)k8, (const uint8_t*)v8, nkv, S, hd, Tk,
+                                     (uint16_t*)k16, (uint16_t*)v16));
   return (int)hipGetLastError();
 }
 

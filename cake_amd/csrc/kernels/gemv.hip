@@ -39,15 +39,17 @@ CAKE_API int cake_gemv_set_tuning(int kind, int U, int prefetch, int max_blocks)
   return 0;
 }
 
-CAKE_API int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float eps,
-                           const void* wq, const void* wk, const void* wv, int K, int nh,
-                           int nkv, int hd, const float* inv_freq, const int* pos,
-                           float* q_out, void* kcache, void* vcache, int S,
-                           hipStream_t st) {
-  if (K % 8 || hd % 2) return (int)hipErrorInvalidValue;
+// kv_fmt (common.h KvFmt): 0 = 16-bit cache rows, 1 = kcache / vcache hold one e4m3fn code
+// per element (quant_kv_fp8 of the f32 roped K / f32 V), 2 = those codes' values as 16 bits
+CAKE_API int cake_qkv_rope_kvf(int dt, const float* resid, const void* norm_w, float eps,
+                               const void* wq, const void* wk, const void* wv, int K, int nh,
+                               int nkv, int hd, const float* inv_freq, const int* pos,
+                               float* q_out, void* kcache, void* vcache, int S,
+                               hipStream_t st, int kv_fmt) {
+  if (K % 8 || hd % 2 || kv_fmt < 0 || kv_fmt > 2) return (int)hipErrorInvalidValue;
   QkvArgs a{resid, (const uint16_t*)norm_w, eps, (const uint16_t*)wq,
             (const uint16_t*)wk, (const uint16_t*)wv, K, nh, nkv, hd, inv_freq, pos,
-            q_out, (uint16_t*)kcache, (uint16_t*)vcache, S};
+            q_out, (uint16_t*)kcache, (uint16_t*)vcache, S, kv_fmt};
   const int npairs = (nh + 2 * nkv) * (hd / 2);
   const size_t lds = (size_t)K * sizeof(float);
   const GemvTune t = g_tune[kQkv];
@@ -55,6 +57,15 @@ CAKE_API int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float
                                                       dim3(grid_for(npairs, t.MB)),
                                                       dim3(kGemvThreads), lds, st, a))));
   return (int)hipGetLastError();
+}
+
+CAKE_API int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float eps,
+                           const void* wq, const void* wk, const void* wv, int K, int nh,
+                           int nkv, int hd, const float* inv_freq, const int* pos,
+                           float* q_out, void* kcache, void* vcache, int S,
+                           hipStream_t st) {
+  return cake_qkv_rope_kvf(dt, resid, norm_w, eps, wq, wk, wv, K, nh, nkv, hd, inv_freq, pos,
+                           q_out, kcache, vcache, S, st, 0);
 }
 
 

@@ -229,6 +229,7 @@ struct QkvArgs {
   uint16_t* kcache;       // [nkv][S][hd] (this layer)
   uint16_t* vcache;
   int S;
+  int kv_fmt;             // KvFmt of the cache (common.h); 1: kcache / vcache hold bytes
 };
 
 struct QkvRow {
@@ -303,8 +304,7 @@ __global__ __launch_bounds__(kGemvThreads) void qkv_rope_kernel(QkvArgs a) {
     } else {
       uint16_t* cache = r.kind == 1 ? a.kcache : a.vcache;
       const size_t off = ((size_t)r.head * a.S + pos) * a.hd + r.i;
-      cache[off] = from_f32<DT>(oa);
-      cache[off + half] = from_f32<DT>(ob);
+      kv_store_pair<DT>(cache, off, half, oa, ob, a.kv_fmt);
     }
   };
   run_pairs<DT, true, U, PFC>(map, epi, xs, a.K, npairs, p0, gridDim.x * kGemvWaves, pre);

@@ -256,6 +256,7 @@ struct QkvW4Args {
   uint16_t* kcache;       // [nkv][S][hd] (this layer)
   uint16_t* vcache;
   int S;
+  int kv_fmt;             // KvFmt of the cache (common.h); 1: kcache / vcache hold bytes
 };
 
 template <int DT, int U, int PFC, int NX>
@@ -320,8 +321,7 @@ __global__ __launch_bounds__(kGemvThreads) void qkv_rope_w4_kernel(QkvW4Args a) 
     } else {
       uint16_t* cache = kind == 1 ? a.kcache : a.vcache;
       const size_t off = ((size_t)head * a.S + pos) * a.hd + i;
-      cache[off] = from_f32<DT>(oa);
-      cache[off + half] = from_f32<DT>(ob);
+      kv_store_pair<DT>(cache, off, half, oa, ob, a.kv_fmt);
     }
   };
   run_pairs_w4<DT, true, U, PFC>(map, epi, xs, a.K, npairs, p0, gridDim.x * kGemvWaves, pre);

@@ -30,15 +30,17 @@ CAKE_API int cake_gemv_w8_get_tuning(int kind, int* out3) {
   return 0;
 }
 
-CAKE_API int cake_qkv_rope_w8(int dt, const float* resid, const void* norm_w, float eps,
-                              const void* wq, const void* wk, const void* wv, const float* sq,
-                              const float* sk, const float* sv, int K, int nh, int nkv, int hd,
-                              const float* inv_freq, const int* pos, float* q_out, void* kcache,
-                              void* vcache, int S, hipStream_t st) {
-  if (K < 16 || K % 16 || hd % 2 || nh < 1 || nkv < 1) return (int)hipErrorInvalidValue;
+// kv_fmt: the cache's format, as cake_qkv_rope_kvf (gemv.hip)
+CAKE_API int cake_qkv_rope_w8_kvf(int dt, const float* resid, const void* norm_w, float eps,
+                                  const void* wq, const void* wk, const void* wv, const float* sq,
+                                  const float* sk, const float* sv, int K, int nh, int nkv, int hd,
+                                  const float* inv_freq, const int* pos, float* q_out,
+                                  void* kcache, void* vcache, int S, hipStream_t st, int kv_fmt) {
+  if (K < 16 || K % 16 || hd % 2 || nh < 1 || nkv < 1 || kv_fmt < 0 || kv_fmt > 2)
+    return (int)hipErrorInvalidValue;
   QkvW8Args a{resid, (const uint16_t*)norm_w, eps, (const uint8_t*)wq, (const uint8_t*)wk,
               (const uint8_t*)wv, sq, sk, sv, K, nh, nkv, hd, inv_freq, pos, q_out,
-              (uint16_t*)kcache, (uint16_t*)vcache, S};
+              (uint16_t*)kcache, (uint16_t*)vcache, S, kv_fmt};
   const int npairs = (nh + 2 * nkv) * (hd / 2);
   const size_t lds = x32_lds_bytes(K);
   const GemvTune t = g_tune_w8[kQkvW8];
@@ -46,4 +48,13 @@ CAKE_API int cake_qkv_rope_w8(int dt, const float* resid, const void* norm_w, fl
                                                          dim3(grid_for(npairs, t.MB)),
                                                          dim3(kGemvThreads), lds, st, a))));
   return (int)hipGetLastError();
+}
+
+CAKE_API int cake_qkv_rope_w8(int dt, const float* resid, const void* norm_w, float eps,
+                              const void* wq, const void* wk, const void* wv, const float* sq,
+                              const float* sk, const float* sv, int K, int nh, int nkv, int hd,
+                              const float* inv_freq, const int* pos, float* q_out, void* kcache,
+                              void* vcache, int S, hipStream_t st) {
+  return cake_qkv_rope_w8_kvf(dt, resid, norm_w, eps, wq, wk, wv, sq, sk, sv, K, nh, nkv, hd,
+                              inv_freq, pos, q_out, kcache, vcache, S, st, 0);
 }

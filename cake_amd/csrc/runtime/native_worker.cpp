@@ -114,6 +114,7 @@ int run_native_worker(const NativeWorkerOpts& o, const TopoNode& node) {
   eo.device = o.device;
   eo.steps_per_graph = 1;
   eo.weight_fmt = o.weight_fmt;
+  eo.kv_fmt = o.kv_fmt;
   char err[1024] = {0};
   void* eng = open_layers(o.model_dir.c_str(), &eo, layers.data(), (int32_t)layers.size(),
                           err, sizeof(err));

@@ -109,6 +109,10 @@ const Flag kFlags[] = {
      "native Llama engine: the lm_head as fp8 (e4m3, one scale per vocabulary row) or mxfp4, "
      "quantised on load, chosen independently of --weight-dtype (not with --parallel tp; "
      "workers hold no head and ignore it); model = --dtype"},
+    {"--kv-dtype", "kv_dtype", PyArg::kStr, "model", "model|fp8", false,
+     "native Llama engine: fp8 = the KV cache as one e4m3 code per element, no scale (half the "
+     "cache), chosen independently of --weight-dtype / --head-dtype (not with --parallel tp; "
+     "each worker's own flag governs its own caches); model = --dtype"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -195,6 +199,8 @@ int env_int(const char* k, int def) {
 // --weight-dtype / --head-dtype -> CakeEngineOpts.weight_fmt / head_fmt (the choices are
 // checked by the parser)
 int32_t weight_fmt_of(const std::string& v) { return v == "fp8" ? 1 : (v == "mxfp4" ? 2 : 0); }
+// --kv-dtype -> CakeEngineOpts.kv_fmt (2, the test oracle, has no CLI value)
+int32_t kv_fmt_of(const std::string& v) { return v == "fp8" ? 1 : 0; }
 
 struct StreamCtx {
   std::string model;
@@ -303,6 +309,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
                       env_int("LOCAL_RANK", rank), 1};
     eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
     eo.head_fmt = weight_fmt_of(o["head_dtype"].value);  // pp: ignored off rank 0; tp: refused
+    eo.kv_fmt = kv_fmt_of(o["kv_dtype"].value);          // pp: this rank's caches; tp: refused
     CakePipeOpts po{rank, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
                     owners.empty() ? nullptr : owners.data(), (int32_t)owners.size()};
     CakeTPOpts to{rank, world, ctl.c_str(), 60.0, 600.0};
@@ -341,6 +348,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   eo.steps_per_graph = 1;
   eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
   eo.head_fmt = weight_fmt_of(o["head_dtype"].value);
+  eo.kv_fmt = kv_fmt_of(o["kv_dtype"].value);
   char err[1024] = {0};
   const auto t0 = std::chrono::steady_clock::now();
   CakePipeOpts po{0, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
@@ -454,6 +462,7 @@ int run_native_worker(cake::PyArgs& o, const cake::TopoNode& node) {
   w.max_seq = o["max_seq_len"].kind == PyArg::kNone ? 4096 : std::atoi(o["max_seq_len"].value.c_str());
   w.bf16 = o["dtype"].value == "bf16";
   w.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
+  w.kv_fmt = kv_fmt_of(o["kv_dtype"].value);
   return cake::run_native_worker(w, node);
 }
 

@@ -24,7 +24,7 @@ TOKEN_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
 class EngineOpts(C.Structure):
     _fields_ = [("max_seq", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32),
                 ("steps_per_graph", C.c_int32), ("init", C.c_int32), ("weight_fmt", C.c_int32),
-                ("seed", C.c_uint64), ("head_fmt", C.c_int32)]
+                ("seed", C.c_uint64), ("head_fmt", C.c_int32), ("kv_fmt", C.c_int32)]
 
 
 class PipeOpts(C.Structure):
@@ -59,6 +59,8 @@ class EngineStats(C.Structure):
 
 # CakeEngineOpts.weight_fmt and .head_fmt
 WEIGHT_FORMATS = {"model": 0, "fp8": 1, "mxfp4": 2}
+# CakeEngineOpts.kv_fmt ("fp8-emulated": the test oracle of "fp8", no CLI value)
+KV_FORMATS = {"model": 0, "fp8": 1, "fp8-emulated": 2}
 
 _lib = None
 
@@ -91,6 +93,16 @@ def lib() -> C.CDLL:
         L.cake_engine_eos.restype = I
         L.cake_engine_weight_bytes.argtypes = [P]
         L.cake_engine_weight_bytes.restype = C.c_int64
+        L.cake_engine_kv_bytes.argtypes = [P]
+        L.cake_engine_kv_bytes.restype = C.c_int64
+        L.cake_engine_open_layers.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
+                                              C.POINTER(C.c_int32), I, C.c_char_p, I]
+        L.cake_engine_open_layers.restype = P
+        L.cake_engine_forward.argtypes = [P, C.c_uint64, C.POINTER(C.c_int32), I, I,
+                                          C.POINTER(C.c_float), I, C.c_char_p, I]
+        L.cake_engine_forward.restype = I
+        L.cake_engine_drop_session.argtypes = [P, C.c_uint64]
+        L.cake_engine_drop_session.restype = None
         L.cake_engine_generate.argtypes = [P, C.POINTER(C.c_int32), I, I, C.POINTER(EngineSampling),
                                            C.POINTER(C.c_int32), I, TOKEN_CB, P,
                                            C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
@@ -135,7 +147,8 @@ class NativeLlama:
                  tp: bool = False, owners: list[int] | None = None, random_init: bool = False,
                  seed: int = 0, worker_of: list[int] | None = None,
                  workers: list[str] | None = None, remote_timeout_s: float = 120.0,
-                 weights: str = "model", head: str = "model"):
+                 weights: str = "model", head: str = "model", kv: str = "model",
+                 layers: list[int] | None = None):
         """world > 1: one rank of a layer-sharded pipeline, or with tp=True of a tensor-
         parallel group (rank 0 generates; the others call :meth:`serve`).  Every rank of
         one group must be constructed concurrently.  ``owners`` (pipeline): the rank of
@@ -155,7 +168,18 @@ class NativeLlama:
         (e4m3fn codes and one f32 scale per vocabulary row) or "mxfp4" (hidden width
         divisible by 32), quantised on load.  The embedding stays in ``dtype``; with tied
         embeddings the quantised head is an extra allocation.  Ranks without the head ignore
-        it; not available with ``tp=True``."""
+        it; not available with ``tp=True``.
+        ``kv``: the KV cache's format, chosen independently of both: "model" keeps it in
+        ``dtype``; "fp8" stores one OCP e4m3fn code per element with no scale
+        (``code = rne_e4m3(clamp(x, -448, 448))`` of the f32 value the writer holds), half
+        the bytes, and every attention read — prefill included — sees the quantised values.
+        "fp8-emulated" is the test oracle of "fp8" and nothing else: the 16-bit cache and
+        its readers with every writer storing the code's value; it saves no memory, and an
+        "fp8" engine equals it bit for bit.  Each pipeline rank's or worker's own value
+        governs its own caches.  Not available with ``tp=True`` nor with the experimental
+        decode launches of docs/ENV.md.
+        ``layers`` (single process): open as a TCP worker's engine holding only these layers
+        (no embedding, no head); drive it with :meth:`forward`."""
         if dtype not in ("bf16", "f16"):
             raise ValueError("native engine dtype: bf16 or f16")
         if weights not in WEIGHT_FORMATS:
@@ -163,12 +187,15 @@ class NativeLlama:
                              f"got {weights!r}")
         if head not in WEIGHT_FORMATS:
             raise ValueError(f"native engine head: one of {sorted(WEIGHT_FORMATS)}, got {head!r}")
+        if kv not in KV_FORMATS:
+            raise ValueError(f"native engine kv: one of {sorted(KV_FORMATS)}, got {kv!r}")
         self.weights = weights
         self.head = head
+        self.kv = kv
         opts = EngineOpts(int(max_seq), 0 if dtype == "bf16" else 1, int(device),
                           max(1, int(steps_per_graph)), 1 if random_init else 0,
                           WEIGHT_FORMATS[weights], int(seed) & 0xFFFFFFFFFFFFFFFF,
-                          WEIGHT_FORMATS[head])
+                          WEIGHT_FORMATS[head], KV_FORMATS[kv])
         err = C.create_string_buffer(1024)
         self._h = None
         if world > 1 and tp:
@@ -189,6 +216,10 @@ class NativeLlama:
                             len(owners) if owners is not None else 0)
             self._h = lib().cake_engine_open_pp(str(model_dir).encode(), C.byref(opts),
                                                 C.byref(pipe), err, len(err))
+        elif layers is not None:
+            ls = (C.c_int32 * len(layers))(*[int(x) for x in layers])
+            self._h = lib().cake_engine_open_layers(str(model_dir).encode(), C.byref(opts), ls,
+                                                    len(layers), err, len(err))
         elif workers:
             wo = (C.c_int32 * len(worker_of))(*[int(x) for x in worker_of])
             hs = (C.c_char_p * len(workers))(*[w.encode() for w in workers])
@@ -219,6 +250,27 @@ class NativeLlama:
         ``"mxfp4"``: one byte per 32 elements), and a quantised head with its scales
         (``head="fp8"`` / ``"mxfp4"``; counted also when the embeddings are tied)."""
         return int(lib().cake_engine_weight_bytes(self._h))
+
+    def kv_bytes(self) -> int:
+        """Bytes of one session's K + V cache on this rank: 2 x local layers x kv heads x
+        max_seq x head_dim x element size (1 with ``kv="fp8"``, else 2)."""
+        return int(lib().cake_engine_kv_bytes(self._h))
+
+    def forward(self, layers: list[int], pos0: int, hidden, session: int = 1):
+        """Worker compute (an engine opened with ``layers``): run `layers` over `hidden`
+        (float32 numpy [T, H], updated in place and returned) at positions pos0.. with the
+        KV cache of `session`.  T > 1 is a prefill chunk, T == 1 a decode step."""
+        import numpy as np
+        if hidden.dtype != np.float32 or hidden.ndim != 2 or not hidden.flags.c_contiguous:
+            raise ValueError("forward: hidden must be a C-contiguous float32 [T, H] array")
+        ls = (C.c_int32 * len(layers))(*[int(x) for x in layers])
+        err = C.create_string_buffer(1024)
+        rc = lib().cake_engine_forward(self._h, int(session), ls, len(layers), int(pos0),
+                                       hidden.ctypes.data_as(C.POINTER(C.c_float)),
+                                       hidden.shape[0], err, len(err))
+        if rc:
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        return hidden
 
     def walk(self) -> str:
         """The token's walk as "rank:first-last" layer runs (comma separated)."""

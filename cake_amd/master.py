@@ -149,6 +149,9 @@ def _load_text(ctx):
     if getattr(ctx, "head_dtype", "model") != "model":
         from .cli import needs_native
         raise RuntimeError(needs_native(ctx.head_dtype, "--head-dtype"))
+    if getattr(ctx, "kv_dtype", "model") != "model":
+        from .cli import needs_native
+        raise RuntimeError(needs_native(ctx.kv_dtype, "--kv-dtype"))
     from .models.llama3.generator import LLamaGenerator
     return LLamaGenerator.load(ctx)
 

@@ -177,3 +177,13 @@ _SIGS.update({
     "cake_gemv_w4_set_tuning": [I, I, I, I],
     "cake_gemv_w4_get_tuning": [I, P],
 })
+# FP8 e4m3 KV cache: the writers' *_kvf twins (trailing kv_fmt), the prefill read and the
+# decode attention over code caches (gemv*.hip, elementwise.hip, attention.hip)
+_SIGS.update({
+    "cake_qkv_rope_kvf": _SIGS["cake_qkv_rope"] + [I],
+    "cake_qkv_rope_w8_kvf": _SIGS["cake_qkv_rope_w8"] + [I],
+    "cake_qkv_rope_w4_kvf": _SIGS["cake_qkv_rope_w4"] + [I],
+    "cake_rope_kv_kvf": _SIGS["cake_rope_kv"] + [I],
+    "cake_dequant_kv_fp8": [I, P, P, I, I, I, I, P, P, P],
+    "cake_attn_decode_kv8": _SIGS["cake_attn_decode"],
+})

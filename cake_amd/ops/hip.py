@@ -51,10 +51,24 @@ def _req(t: torch.Tensor, name: str, *, dtype=None, numel=None, shape=None) -> N
 # decode (batch 1) fused projections
 # ---------------------------------------------------------------------------
 
-def qkv_rope(resid, norm_w, eps, wq, wk, wv, inv_freq, pos, q_out, kcache, vcache):
+KV_FMT_16, KV_FMT_FP8, KV_FMT_FP8_EMULATED = 0, 1, 2
+
+
+def _kv_cache_dtype(kv_fmt: int, dt):
+    """Element type of a KV cache of format `kv_fmt`: uint8 codes for the FP8 cache (1), the
+    model dtype for the 16-bit cache (0) and for its FP8-valued test oracle (2)."""
+    if kv_fmt not in (KV_FMT_16, KV_FMT_FP8, KV_FMT_FP8_EMULATED):
+        raise ValueError(f"kv_fmt must be 0 (16-bit), 1 (fp8 e4m3) or 2 (fp8 values in a 16-bit "
+                         f"cache), got {kv_fmt}")
+    return torch.uint8 if kv_fmt == KV_FMT_FP8 else dt
+
+
+def qkv_rope(resid, norm_w, eps, wq, wk, wv, inv_freq, pos, q_out, kcache, vcache, kv_fmt=0):
     """rmsnorm(resid) -> q/k/v GEMV -> RoPE(pos) -> q_out f32, k/v into cache[:, pos].
 
-    kcache/vcache: [nkv, S, hd] (one layer). pos: int32 device scalar.
+    kcache/vcache: [nkv, S, hd] (one layer). pos: int32 device scalar.  kv_fmt 1: uint8
+    caches that receive ``reference.quant_kv_fp8`` of the f32 roped K / f32 V; 2: 16-bit
+    caches that receive those codes' values.
     """
     K = resid.numel()
     nkv, S, hd = kcache.shape
@@ -68,14 +82,20 @@ def qkv_rope(resid, norm_w, eps, wq, wk, wv, inv_freq, pos, q_out, kcache, vcach
     _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
     _req(pos, "pos", dtype=torch.int32, numel=1)
     _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
-    _req(kcache, "kcache", dtype=dt)
-    _req(vcache, "vcache", dtype=dt, shape=kcache.shape)
+    _req(kcache, "kcache", dtype=_kv_cache_dtype(kv_fmt, dt))
+    _req(vcache, "vcache", dtype=kcache.dtype, shape=kcache.shape)
     if K % 8:
         raise ValueError("hidden size must be a multiple of 8")
-    check(kernels().cake_qkv_rope(_dt(wq), _p(resid), _p(norm_w), float(eps), _p(wq), _p(wk),
-                                  _p(wv), K, nh, nkv, hd, _p(inv_freq), _p(pos), _p(q_out),
-                                  _p(kcache), _p(vcache), S, _stream()),
-          "qkv_rope")
+    if kv_fmt == 0:
+        check(kernels().cake_qkv_rope(_dt(wq), _p(resid), _p(norm_w), float(eps), _p(wq), _p(wk),
+                                      _p(wv), K, nh, nkv, hd, _p(inv_freq), _p(pos), _p(q_out),
+                                      _p(kcache), _p(vcache), S, _stream()),
+              "qkv_rope")
+        return
+    check(kernels().cake_qkv_rope_kvf(_dt(wq), _p(resid), _p(norm_w), float(eps), _p(wq), _p(wk),
+                                      _p(wv), K, nh, nkv, hd, _p(inv_freq), _p(pos), _p(q_out),
+                                      _p(kcache), _p(vcache), S, _stream(), int(kv_fmt)),
+          "qkv_rope_kvf")
 
 
 
@@ -223,6 +243,40 @@ def attn_oproj_short(pos: int) -> bool:
     return attn_splits(int(pos) + 2) == 1
 
 
+def _attn_env_once() -> None:
+    if not _ATTN_IMPL_SET[0]:  # CAKE_ATTN_IMPL / CAKE_ATTN_TARGET, applied once
+        attn_set_impl(_ATTN_IMPL[0])
+        if os.environ.get("CAKE_ATTN_TARGET"):
+            attn_set_target_splits(int(os.environ["CAKE_ATTN_TARGET"]))
+        if os.environ.get("CAKE_ATTN_SINGLE"):
+            attn_set_single_max(int(os.environ["CAKE_ATTN_SINGLE"]))
+        if os.environ.get("CAKE_ATTN_PREFETCH"):
+            attn_set_prefetch(int(os.environ["CAKE_ATTN_PREFETCH"]))
+
+
+def attn_decode_kv8(q, kcache8, vcache8, pos, scale, part, tickets, out):
+    """:func:`attn_decode` over an FP8 KV cache: kcache8 / vcache8 uint8 [nkv, S, hd] hold
+    one e4m3fn code per element; `out` (bf16 / f16) names the model dtype.  Core 2 only (an
+    error under ``attn_set_impl(1)``).  The output equals, bit for bit, :func:`attn_decode`
+    on 16-bit caches holding the codes' values."""
+    nkv, S, hd = kcache8.shape
+    nh = q.numel() // hd
+    _req(q, "q", dtype=torch.float32)
+    _req(kcache8, "kcache8", dtype=torch.uint8)
+    _req(vcache8, "vcache8", dtype=torch.uint8, shape=kcache8.shape)
+    _req(pos, "pos", dtype=torch.int32, numel=1)
+    _req(part, "part", dtype=torch.float32, numel=attn_workspace_numel(nh, hd, S))
+    _req(out, "out", numel=nh * hd)
+    _req(tickets, "tickets", dtype=torch.int32, numel=2 * nkv + 2)
+    if hd not in (64, 128) or nh % nkv or (nh // nkv) not in (1, 2, 4, 8):
+        raise ValueError(f"unsupported attention shape nh={nh} nkv={nkv} hd={hd}")
+    _attn_env_once()
+    check(kernels().cake_attn_decode_kv8(_dt(out), _p(q), _p(kcache8), _p(vcache8), _p(pos), S,
+                                         nh, nkv, hd, float(scale), _p(part), _p(tickets),
+                                         _p(out), _stream()),
+          "attn_decode_kv8")
+
+
 def attn_decode(q, kcache, vcache, pos, scale, part, tickets, out):
     """Split-K GQA decode attention for the token at device position `pos`.
 
@@ -244,14 +298,7 @@ def attn_decode(q, kcache, vcache, pos, scale, part, tickets, out):
     _req(tickets, "tickets", dtype=torch.int32, numel=2 * nkv + 2)
     if hd not in (64, 128) or nh % nkv or (nh // nkv) not in (1, 2, 4, 8):
         raise ValueError(f"unsupported attention shape nh={nh} nkv={nkv} hd={hd}")
-    if not _ATTN_IMPL_SET[0]:  # CAKE_ATTN_IMPL / CAKE_ATTN_TARGET, applied once
-        attn_set_impl(_ATTN_IMPL[0])
-        if os.environ.get("CAKE_ATTN_TARGET"):
-            attn_set_target_splits(int(os.environ["CAKE_ATTN_TARGET"]))
-        if os.environ.get("CAKE_ATTN_SINGLE"):
-            attn_set_single_max(int(os.environ["CAKE_ATTN_SINGLE"]))
-        if os.environ.get("CAKE_ATTN_PREFETCH"):
-            attn_set_prefetch(int(os.environ["CAKE_ATTN_PREFETCH"]))
+    _attn_env_once()
     check(kernels().cake_attn_decode(_dt(kcache), _p(q), _p(kcache), _p(vcache), _p(pos), S,
                                      nh, nkv, hd, float(scale), _p(part), _p(tickets),
                                      _p(out), _stream()),
@@ -487,25 +534,49 @@ def _rows(t: torch.Tensor, name: str, cols: int, T: int, dtype) -> int:
     return t.stride(0)
 
 
-def rope_kv(q, k, v, inv_freq, pos0: int, kcache, vcache):
+def rope_kv(q, k, v, inv_freq, pos0: int, kcache, vcache, kv_fmt=0):
     """q [T, nh*hd] roped in place; k roped / v copied into cache rows pos0..pos0+T-1.
 
     q, k, v may be column slices of one fused [T, (nh + 2 nkv) hd] projection
-    or separate contiguous tensors (k and v share a row stride)."""
+    or separate contiguous tensors (k and v share a row stride).  kv_fmt 1: uint8 caches
+    that receive ``reference.quant_kv_fp8`` of the f32 rotation of k and of v widened to
+    f32; 2: 16-bit caches that receive those codes' values (hd % 16 == 0 for both)."""
     nkv, S, hd = kcache.shape
     T = q.shape[0]
     nh = q.shape[1] // hd
     if pos0 < 0 or pos0 + T > S:
         raise ValueError(f"positions {pos0}..{pos0 + T} exceed cache length {S}")
-    ldq = _rows(q, "q", nh * hd, T, kcache.dtype)
-    ld = _rows(k, "k", nkv * hd, T, kcache.dtype)
-    if _rows(v, "v", nkv * hd, T, kcache.dtype) != ld and T > 1:
+    if kv_fmt != 0 and hd % 16:
+        raise ValueError("an fp8 KV cache needs a head dimension divisible by 16")
+    dt = kcache.dtype if kv_fmt == 0 else q.dtype  # the model dtype
+    ldq = _rows(q, "q", nh * hd, T, dt)
+    ld = _rows(k, "k", nkv * hd, T, dt)
+    if _rows(v, "v", nkv * hd, T, dt) != ld and T > 1:
         raise ValueError("rope_kv: k and v need the same row stride")
     _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
-    _req(kcache, "kcache")
-    _req(vcache, "vcache", shape=kcache.shape)
+    _req(kcache, "kcache", dtype=_kv_cache_dtype(kv_fmt, dt))
+    _req(vcache, "vcache", dtype=kcache.dtype, shape=kcache.shape)
+    if kv_fmt != 0:
+        check(kernels().cake_rope_kv_kvf(_dt(q), _p(q), _p(k), _p(v), ldq, ld, T, nh, nkv, hd,
+                                         _p(inv_freq), int(pos0), S, _p(kcache), _p(vcache),
+                                         _stream(), int(kv_fmt)), "rope_kv_kvf")
+        return
     check(kernels().cake_rope_kv(_dt(q), _p(q), _p(k), _p(v), ldq, ld, T, nh, nkv, hd, _p(inv_freq),
                                  int(pos0), S, _p(kcache), _p(vcache), _stream()), "rope_kv")
+
+
+def dequant_kv_fp8(kcache8, vcache8, Tk: int, k16, v16):
+    """Rows [0, Tk) of every kv head of the uint8 code caches [nkv, S, hd] widened (exactly)
+    into the 16-bit scratches k16 / v16 of the same shape; their rows >= Tk are untouched."""
+    nkv, S, hd = kcache8.shape
+    _req(kcache8, "kcache8", dtype=torch.uint8)
+    _req(vcache8, "vcache8", dtype=torch.uint8, shape=kcache8.shape)
+    _req(k16, "k16", shape=kcache8.shape)
+    _req(v16, "v16", dtype=k16.dtype, shape=kcache8.shape)
+    if hd % 16 or not 1 <= Tk <= S:
+        raise ValueError(f"dequant_kv_fp8: hd {hd} % 16 != 0 or Tk {Tk} outside 1..{S}")
+    check(kernels().cake_dequant_kv_fp8(_dt(k16), _p(kcache8), _p(vcache8), nkv, S, hd, int(Tk),
+                                        _p(k16), _p(v16), _stream()), "dequant_kv_fp8")
 
 
 def silu_mul(g, u, out):
@@ -724,7 +795,8 @@ def dequant_rows_fp8(w8, scale, out16):
                                           _stream()), "dequant_rows_fp8")
 
 
-def qkv_rope_w8(resid, norm_w, eps, wq, wk, wv, sq, sk, sv, inv_freq, pos, q_out, kcache, vcache):
+def qkv_rope_w8(resid, norm_w, eps, wq, wk, wv, sq, sk, sv, inv_freq, pos, q_out, kcache, vcache,
+                kv_fmt=0):
     """:func:`qkv_rope` over fp8 weights: wq / wk / wv uint8 codes, sq / sk / sv their f32
     row scales; the model dtype is the norm weight's and the cache's."""
     K = resid.numel()
@@ -739,8 +811,15 @@ def qkv_rope_w8(resid, norm_w, eps, wq, wk, wv, sq, sk, sv, inv_freq, pos, q_out
     _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
     _req(pos, "pos", dtype=torch.int32, numel=1)
     _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
-    _req(kcache, "kcache", dtype=dt)
-    _req(vcache, "vcache", dtype=dt, shape=kcache.shape)
+    _req(kcache, "kcache", dtype=_kv_cache_dtype(kv_fmt, dt))
+    _req(vcache, "vcache", dtype=kcache.dtype, shape=kcache.shape)
+    if kv_fmt != 0:  # the cache's format: see qkv_rope
+        check(kernels().cake_qkv_rope_w8_kvf(_dt(norm_w), _p(resid), _p(norm_w), float(eps),
+                                             _p(wq), _p(wk), _p(wv), _p(sq), _p(sk), _p(sv), K,
+                                             nh, nkv, hd, _p(inv_freq), _p(pos), _p(q_out),
+                                             _p(kcache), _p(vcache), S, _stream(), int(kv_fmt)),
+              "qkv_rope_w8_kvf")
+        return
     check(kernels().cake_qkv_rope_w8(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wq),
                                      _p(wk), _p(wv), _p(sq), _p(sk), _p(sv), K, nh, nkv, hd,
                                      _p(inv_freq), _p(pos), _p(q_out), _p(kcache), _p(vcache), S,
@@ -867,7 +946,8 @@ def dequant_rows_mxfp4(w4, e8, out16):
                                             _stream()), "dequant_rows_mxfp4")
 
 
-def qkv_rope_w4(resid, norm_w, eps, wq, wk, wv, eq, ek, ev, inv_freq, pos, q_out, kcache, vcache):
+def qkv_rope_w4(resid, norm_w, eps, wq, wk, wv, eq, ek, ev, inv_freq, pos, q_out, kcache, vcache,
+                kv_fmt=0):
     """:func:`qkv_rope` over MXFP4 weights: wq / wk / wv packed codes, eq / ek / ev their
     block-scale bytes; the model dtype is the norm weight's and the cache's."""
     K = resid.numel()
@@ -882,8 +962,15 @@ def qkv_rope_w4(resid, norm_w, eps, wq, wk, wv, eq, ek, ev, inv_freq, pos, q_out
     _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
     _req(pos, "pos", dtype=torch.int32, numel=1)
     _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
-    _req(kcache, "kcache", dtype=dt)
-    _req(vcache, "vcache", dtype=dt, shape=kcache.shape)
+    _req(kcache, "kcache", dtype=_kv_cache_dtype(kv_fmt, dt))
+    _req(vcache, "vcache", dtype=kcache.dtype, shape=kcache.shape)
+    if kv_fmt != 0:  # the cache's format: see qkv_rope
+        check(kernels().cake_qkv_rope_w4_kvf(_dt(norm_w), _p(resid), _p(norm_w), float(eps),
+                                             _p(wq), _p(wk), _p(wv), _p(eq), _p(ek), _p(ev), K,
+                                             nh, nkv, hd, _p(inv_freq), _p(pos), _p(q_out),
+                                             _p(kcache), _p(vcache), S, _stream(), int(kv_fmt)),
+              "qkv_rope_w4_kvf")
+        return
     check(kernels().cake_qkv_rope_w4(_dt(norm_w), _p(resid), _p(norm_w), float(eps), _p(wq),
                                      _p(wk), _p(wv), _p(eq), _p(ek), _p(ev), K, nh, nkv, hd,
                                      _p(inv_freq), _p(pos), _p(q_out), _p(kcache), _p(vcache), S,

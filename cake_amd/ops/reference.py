@@ -148,3 +148,15 @@ def apply_repeat_penalty(logits: torch.Tensor, penalty: float, context: list[int
             s = out[..., t]
             out[..., t] = torch.where(s >= 0, s / penalty, s * penalty)
     return out
+
+
+def quant_kv_fp8(x: torch.Tensor) -> torch.Tensor:
+    """FP8 KV-cache storage (the oracle of every kv_fmt = 1 writer): one OCP e4m3fn code per
+    element and no scale, ``code = rne_e4m3(clamp(float(x), -448, 448))`` — clamped before the
+    conversion, so a finite input never gives the NaN code.  Returns uint8, x's shape."""
+    return x.float().clamp(-FP8_E4M3_MAX, FP8_E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+
+
+def dequant_kv_fp8(codes: torch.Tensor) -> torch.Tensor:
+    """f32 = fp8(code); every value is exact in bf16 and in f16."""
+    return codes.view(torch.float8_e4m3fn).float()
