@@ -557,6 +557,8 @@ CAKE_API int cake_rmsnorm(int dt, const float* x, const void* w, float eps, int 
 CAKE_API int cake_rope_kv(int dt, void* q, const void* k, const void* v, int ldq, int ld, int T, int nh,
                           int nkv, int hd, const float* inv_freq, int pos0, int S, void* kc,
                           void* vc, hipStream_t st) {
+  // rows pos0 .. pos0 + T - 1 of the [nkv][S][hd] caches are written: none outside them
+  if (pos0 < 0 || (long long)pos0 + T > S) return (int)hipErrorInvalidValue;
   const bool vec = hd % 16 == 0 && hd <= 256 && ldq % 8 == 0 && ld % 8 == 0 &&
                    ((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)kc | (uintptr_t)vc) % 16 == 0;
   if (vec) {

@@ -291,15 +291,19 @@ __global__ __launch_bounds__(512) void gn_nhwc_stats_kernel(GnSrc src, int HW,
         raw[u] = pp < p1 ? *reinterpret_cast<const uint4*>(base + (size_t)pp * ld)
                          : make_uint4(0, 0, 0, 0);
       }
-      float a0 = 0.f, b0 = 0.f, a1 = 0.f, b1 = 0.f;
+      // f64 from the first add: the sum of 64 raw squares of f16 inputs with |mean| >> std
+      // does not fit in f32's 24 bits, and var = E[x^2] - mean^2 then came out low by 1-2 %
+      // (mean 200-256, std 0.5-1: outputs 3-12 f16 ulp off); bf16 squares are exact in f32
+      double a0 = 0.0, b0 = 0.0, a1 = 0.0, b1 = 0.0;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         float f[8];
         unpack8<DT>(raw[u], f);  // zero vectors past p1 add nothing
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          if ((cv * 8 + e) / Cg == g0) { a0 += f[e]; b0 += f[e] * f[e]; }
-          else { a1 += f[e]; b1 += f[e] * f[e]; }
+          const double d = (double)f[e];
+          if ((cv * 8 + e) / Cg == g0) { a0 += d; b0 += d * d; }
+          else { a1 += d; b1 += d * d; }
         }
       }
       s0 += a0; q0 += b0; s1 += a1; q1 += b1;
