@@ -101,6 +101,11 @@ def build_parser() -> argparse.ArgumentParser:
            "(half the cache; every attention read sees the quantised values), chosen "
            "independently of --weight-dtype / --head-dtype (not with --parallel tp; each "
            "worker's own flag governs its own caches); model = --dtype")
+    a("--prefill-dtype", choices=["model", "fp8"], default="model",
+      help="native Llama engine: fp8 = the prefill projections on the fp8 matrix instruction, "
+           "the activations quantised per token to e4m3 and multiplied with the resident fp8 "
+           "codes (needs --weight-dtype fp8; not with --parallel tp; each worker's own flag "
+           "governs its own layers); model = the weights' own prefill")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -129,9 +134,9 @@ def run_parsed(opts: dict) -> int:
 
 
 def needs_native(fmt: str, flag: str = "--weight-dtype") -> str:
-    """The refusal of a quantised ``--weight-dtype`` / ``--head-dtype`` / ``--kv-dtype`` (fp8,
-    mxfp4) on a Python engine path."""
-    what = "KV cache" if flag == "--kv-dtype" else "weights"
+    """The refusal of a quantised ``--weight-dtype`` / ``--head-dtype`` / ``--kv-dtype`` /
+    ``--prefill-dtype`` (fp8, mxfp4) on a Python engine path."""
+    what = {"--kv-dtype": "KV cache", "--prefill-dtype": "prefill"}.get(flag, "weights")
     return (f"{flag} {fmt} is served by the native Llama engine only (a GPU, "
             "--dtype f16 or bf16, hipGraph decode, CAKE_NATIVE not 0); this run would "
             f"take the Python path, which has no {fmt} {what}: refusing rather than "
@@ -179,6 +184,14 @@ def kv_dtype_refusal(ctx) -> str | None:
     return _quant_refusal(ctx, "--kv-dtype", getattr(ctx, "kv_dtype", "model"))
 
 
+def prefill_dtype_refusal(ctx) -> str | None:
+    """The same for ``--prefill-dtype``, in the same wording (a native worker runs its own
+    layers' prefill chunks, so ``cake-cli --mode worker`` serves it; the Python worker
+    refuses).  On the native engine it needs ``--weight-dtype fp8``: the engine's own open
+    refuses any other combination."""
+    return _quant_refusal(ctx, "--prefill-dtype", getattr(ctx, "prefill_dtype", "model"))
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -187,7 +200,8 @@ def _run(args) -> int:
     setup_logging(args.log_level)
     from .context import Context
     ctx = Context.from_args(args)
-    why = weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
+    why = (weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
+           or prefill_dtype_refusal(ctx))
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

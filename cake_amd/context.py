@@ -44,6 +44,7 @@ class Context:
     weight_dtype: str = "model"  # --weight-dtype: "fp8" / "mxfp4" = native engine only
     head_dtype: str = "model"    # --head-dtype: the lm_head's format, native engine only
     kv_dtype: str = "model"      # --kv-dtype: "fp8" = e4m3 KV cache, native engine only
+    prefill_dtype: str = "model"  # --prefill-dtype: "fp8" = fp8 MFMA prefill, native engine only
 
     @classmethod
     def from_args(cls, args) -> "Context":
@@ -71,7 +72,8 @@ class Context:
                    no_graph=getattr(args, "no_graph", False),
                    weight_dtype=getattr(args, "weight_dtype", "model") or "model",
                    head_dtype=getattr(args, "head_dtype", "model") or "model",
-                   kv_dtype=getattr(args, "kv_dtype", "model") or "model")
+                   kv_dtype=getattr(args, "kv_dtype", "model") or "model",
+                   prefill_dtype=getattr(args, "prefill_dtype", "model") or "model")
 
 
 def hbm_mib(device=None) -> dict:

@@ -93,6 +93,11 @@ int cake_swiglu_w8(int dt, const float* resid, const void* norm_w, float eps, co
                    hipStream_t st);
 int cake_gemv_x16_w8(int dt, const void* x, const void* w, const float* scale, int K, int N,
                      float* out, int accumulate, hipStream_t st);
+// FP8 x FP8 MFMA GEMM of the quantised prefill (gemm_w8a8.hip): e4m3 activation codes with one
+// f32 scale per token against the resident projection codes; cfg < 0 = its planner's tile
+int cake_gemm_w8a8(int dt, int epi, int cfg, const void* a8, long long lda, const float* sa,
+                   const void* w8, long long ldb, const float* sw, void* c, long long ldc,
+                   float* r32, long long ldr, int M, int N, int K, hipStream_t st);
 // MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
 int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void* e8,
                           hipStream_t st);
@@ -356,6 +361,10 @@ const char* const kNoKvTP =
     "a quantised KV cache (kv_fmt 1 = fp8, 2 = its 16-bit oracle) is not supported with tensor "
     "parallelism: open the tensor-parallel engine with kv_fmt 0";
 
+const char* const kNoPrefillTP =
+    "an fp8 MFMA prefill (prefill_fmt 1) is not supported with tensor parallelism: open the "
+    "tensor-parallel engine with prefill_fmt 0";
+
 Json msg(const char* cmd) {
   Json j = Json::object();
   j.set("cmd", Json::string(cmd));
@@ -370,8 +379,9 @@ class Llama {
   Llama(const std::string& dir, const CakeEngineOpts& o, const CakePipeOpts* pp = nullptr,
         const std::vector<int>* layers = nullptr, const CakeTPOpts* tp = nullptr,
         const CakeRemoteOpts* remote = nullptr)
-      : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(o.weight_fmt), hfmt_(o.head_fmt),
-        kvfmt_(o.kv_fmt), seed_(o.seed) {
+      : dt_(o.dtype), dev_(o.device), init_(o.init), wfmt_(CAKE_WEIGHT_FMT_OF(o.weight_fmt)),
+        hfmt_(o.head_fmt), kvfmt_(o.kv_fmt), pfmt_(CAKE_PREFILL_FMT_OF(o.weight_fmt)),
+        seed_(o.seed) {
     if (dt_ != 0 && dt_ != 1) throw Error("dtype must be 0 (bf16) or 1 (f16)");
     if (wfmt_ != 0 && wfmt_ != 1 && wfmt_ != 2)
       throw Error("weight_fmt must be 0 (model dtype), 1 (fp8 e4m3 projections) or 2 (mxfp4 "
@@ -395,6 +405,13 @@ class Llama {
                       ": unset it or open with kv_fmt 0");
       }
     }
+    if (pfmt_ != 0 && pfmt_ != 1)
+      throw Error("prefill_fmt must be 0 (the weights' prefill) or 1 (fp8 MFMA prefill with "
+                  "per-token e4m3 activations)");
+    if (pfmt_ != 0 && tp) throw Error(kNoPrefillTP);
+    if (pfmt_ == 1 && wfmt_ != 1)
+      throw Error("an fp8 MFMA prefill (prefill_fmt 1) runs on the resident fp8 projection codes: "
+                  "open with weight_fmt 1 (fp8), not " + std::to_string(wfmt_));
     if (init_ != 0 && init_ != 1) throw Error("init must be 0 (checkpoint) or 1 (random)");
     if (tp) {
       tp_ = tp->world;
@@ -442,6 +459,9 @@ class Llama {
     }
     if (wfmt_ == 1 && (cfg_.H % 16 || (cfg_.nh * cfg_.hd) % 16 || cfg_.I % 16))
       throw Error("fp8 weights need hidden, attention and intermediate widths divisible by 16");
+    if (pfmt_ == 1 && (cfg_.H % 128 || (cfg_.nh * cfg_.hd) % 128 || cfg_.I % 128))
+      throw Error("an fp8 MFMA prefill needs hidden, attention and intermediate widths divisible "
+                  "by 128 (the k of one MFMA step)");
     if (wfmt_ == 2 && (cfg_.H % 32 || (cfg_.nh * cfg_.hd) % 32 || cfg_.I % 32))
       throw Error("mxfp4 weights need hidden, attention and intermediate widths divisible by 32");
     if (layers) {  // a TCP worker: the topology node's layers, no embedding / head
@@ -500,7 +520,7 @@ class Llama {
     load_weights(dir);
     // one line per open: what the weights are and what they occupy
     std::fprintf(stderr,
-                 "cake engine: weights %s, lm_head %s, kv cache %s, %lld bytes on device (rank %d, "
+                 "cake engine: weights %s, lm_head %s, kv cache %s%s, %lld bytes on device (rank %d, "
                  "%d layers)\n",
                  wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
                                         : "fp8 e4m3 projections (f16 rest)")
@@ -513,6 +533,7 @@ class Llama {
                  : kvfmt_ == 2 ? (dt_ == 0 ? "fp8 e4m3 values in bf16 (test oracle)"
                                            : "fp8 e4m3 values in f16 (test oracle)")
                                : (dt_ == 0 ? "bf16" : "f16"),
+                 pfmt_ == 1 ? ", prefill fp8 e4m3 activations" : "",
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
@@ -850,6 +871,9 @@ class Llama {
   // kv16_k_ / kv16_v_ (one layer's [nkv][S][hd], allocated once).  2: the 16-bit cache with
   // fp8-valued writers (test oracle).  != 0: never the head-parallel or fused launches.
   int kvfmt_ = 0;
+  // prefill_fmt (bits 8 and up of CakeEngineOpts.weight_fmt).  1: every prefill projection quantises its activation rows
+  // (a8_ codes, sa_ one f32 scale per token) and runs cake_gemm_w8a8 on the resident codes
+  int pfmt_ = 0;
   uint16_t *kv16_k_ = nullptr, *kv16_v_ = nullptr;
   int64_t weight_bytes_ = 0;   // device weight allocations of this rank
   // head_fmt 1: head_q_ holds the e4m3 codes [V, H], head_s_ the f32 row scales; head_fmt 2:
@@ -957,6 +981,8 @@ class Llama {
   float* hidden_ = nullptr;
   void *x16_ = nullptr, *qkv_ = nullptr, *att_ = nullptr, *pact_ = nullptr;
   int32_t* ptok_ = nullptr;
+  uint8_t* a8_ = nullptr;       // prefill_fmt 1: [T, max(H, nq, I)] activation codes
+  float* sa_ = nullptr;         // prefill_fmt 1: [T] activation scales
   float* ws_ = nullptr;
   size_t ws_n_ = 0;
   static constexpr size_t kLibWsBytes = 32u << 20;
@@ -1409,6 +1435,12 @@ class Llama {
     att_ = dalloc<uint16_t>((size_t)T * nq);
     pact_ = dalloc<uint16_t>((size_t)T * c.I);
     ptok_ = dalloc<int32_t>(T);
+    if (pfmt_ == 1) {
+      dfree(a8_);
+      dfree(sa_);
+      a8_ = dalloc<uint8_t>((size_t)T * std::max({(size_t)c.H, nq, (size_t)c.I}));
+      sa_ = dalloc<float>(T);
+    }
     pre_T_ = T;
   }
 
@@ -1571,9 +1603,21 @@ class Llama {
           k_check(cake_dequant_rows_fp8(dt_, wp, sp, N, K, w16_, st_), "dequant_rows_fp8");
         return w16_;
       };
+      // prefill_fmt 1: the activation rows quantised per token (the weights' own row
+      // quantiser over [T, K]), then the fp8 MFMA GEMM on the resident codes: no dequantise
+      // pass, the 16-bit scratch untouched
+      auto gemm8 = [&](int epi, const void* act, const void* wp, const float* sp, void* cptr,
+                       long long ldc, float* resid, long long ldr, int N, int K, const char* what) {
+        k_check(cake_quant_rows_fp8(dt_, act, T, K, a8_, sa_, st_), "quant_rows_fp8 (activations)");
+        k_check(cake_gemm_w8a8(dt_, epi, -1, a8_, K, sa_, wp, K, sp, cptr, ldc, resid, ldr, T, N, K,
+                               st_), what);
+      };
       k_check(cake_rmsnorm(dt_, hidden_, w.ln1, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, w.eqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr,
-           0, T, nqkv, c.H, "gemm qkv");
+      if (pfmt_ == 1)
+        gemm8(kEpiStore, x16_, w.wqkv, w.sqkv, qkv_, nqkv, nullptr, 0, nqkv, c.H, "gemm_w8a8 qkv");
+      else
+        gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, w.eqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr,
+             0, T, nqkv, c.H, "gemm qkv");
       uint16_t* q = reinterpret_cast<uint16_t*>(qkv_);
       // (kv_fmt 0: cake_rope_kv itself)
       k_check(cake_rope_kv_kvf(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
@@ -1599,16 +1643,25 @@ class Llama {
       if (tp_ > 1) {  // partial o_proj over this rank's heads, summed over the ranks
         gemm(kEpiStore32, att_, nq, w.wo, nq, nullptr, 0, ppart_, c.H, T, c.H, nq, "gemm o");
         dense_allreduce(T);
+      } else if (pfmt_ == 1) {
+        gemm8(kEpiResid32, att_, w.wo, w.so, nullptr, 0, hidden_, c.H, c.H, nq, "gemm_w8a8 o");
       } else {
         gemm(kEpiResid32, att_, nq, w16(w.wo, w.so, w.eo, c.H, nq), nq, nullptr, 0, hidden_, c.H, T,
              c.H, nq, "gemm o");
       }
       k_check(cake_rmsnorm(dt_, hidden_, w.ln2, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, w.egu, 2 * c.I, c.H), c.H, pact_, c.I, nullptr,
-           0, T, c.I, c.H, "gemm gate|up");
+      if (pfmt_ == 1)
+        gemm8(kEpiSwiglu, x16_, w.wgu, w.sgu, pact_, c.I, nullptr, 0, c.I, c.H,
+              "gemm_w8a8 gate|up");
+      else
+        gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, w.egu, 2 * c.I, c.H), c.H, pact_, c.I,
+             nullptr, 0, T, c.I, c.H, "gemm gate|up");
       if (tp_ > 1) {
         gemm(kEpiStore32, pact_, c.I, w.wd, c.I, nullptr, 0, ppart_, c.H, T, c.H, c.I, "gemm down");
         dense_allreduce(T);
+      } else if (pfmt_ == 1) {
+        gemm8(kEpiResid32, pact_, w.wd, w.sd, nullptr, 0, hidden_, c.H, c.H, c.I,
+              "gemm_w8a8 down");
       } else {
         gemm(kEpiResid32, pact_, c.I, w16(w.wd, w.sd, w.ed, c.H, c.I), c.I, nullptr, 0, hidden_, c.H,
              T, c.H, c.I, "gemm down");
@@ -2975,7 +3028,8 @@ CAKE_API void* cake_engine_open_tp(const char* model_dir, const CakeEngineOpts* 
                                    const CakeTPOpts* tp, char* err, int32_t errlen) {
   try {
     if (!model_dir || !opts || !tp) throw cake::Error("null argument");
-    if (opts->weight_fmt != 0) throw cake::Error(cake::kNoFp8TP);
+    if (CAKE_WEIGHT_FMT_OF(opts->weight_fmt) != 0) throw cake::Error(cake::kNoFp8TP);
+    if (CAKE_PREFILL_FMT_OF(opts->weight_fmt) != 0) throw cake::Error(cake::kNoPrefillTP);
     if (opts->head_fmt != 0) throw cake::Error(cake::kNoQHeadTP);
     if (opts->kv_fmt != 0) throw cake::Error(cake::kNoKvTP);
     return new Llama(model_dir, *opts, nullptr, nullptr, tp);

@@ -15,6 +15,12 @@ extern "C" {
 
 typedef int32_t (*cake_engine_token_cb)(void* ctx, int32_t token);  // non-zero = stop
 
+// CakeEngineOpts.weight_fmt = weight format | CAKE_PREFILL_FMT(prefill_fmt)
+#define CAKE_PREFILL_FMT_SHIFT 8
+#define CAKE_PREFILL_FMT(p) ((int32_t)((uint32_t)(p) << CAKE_PREFILL_FMT_SHIFT))
+#define CAKE_WEIGHT_FMT_OF(w) ((int32_t)((uint32_t)(w) & 0xffu))
+#define CAKE_PREFILL_FMT_OF(w) ((int32_t)((uint32_t)(w) >> CAKE_PREFILL_FMT_SHIFT))
+
 struct CakeEngineOpts {
   int32_t max_seq;          // KV-cache length (prompt + generated tokens)
   int32_t dtype;            // 0 = bf16, 1 = f16
@@ -29,6 +35,19 @@ struct CakeEngineOpts {
                             // weight-only projections (the same four: two e2m1 codes per
                             // byte + one e8m0 scale byte per 32 elements of a row; widths
                             // divisible by 32), quantised on load.  1, 2: not with open_tp.
+                            // Bits 8 and up of this word are prefill_fmt (the struct's 40
+                            // bytes are full and its layout is fixed; CAKE_PREFILL_FMT below):
+                            // 0: prefill runs the weights' own path (weight_fmt 1, 2: each
+                            // projection widened into a 16-bit scratch before a 16-bit MFMA
+                            // GEMM).  1: FP8 MFMA prefill — every projection quantises its
+                            // activation rows per token (e4m3fn codes, scale = amax / 448) and
+                            // multiplies them with the resident e4m3fn projection codes on the
+                            // fp8 matrix instruction, f32 accumulation, both scales applied to
+                            // the finished sum; no dequantise pass.  Requires weight_fmt 1 and
+                            // hidden, attention and intermediate widths divisible by 128.
+                            // Decode, lm_head and the KV format are unchanged; composes with
+                            // head_fmt / kv_fmt; each pipeline rank's or worker's own value
+                            // governs its own layers.  Not with open_tp.
   uint64_t seed;            // init = 1: weight seed
   int32_t head_fmt;         // 0: lm_head in the model dtype; 1: e4m3fn codes + one f32 scale per
                             // vocabulary row; 2: MXFP4 (hidden width divisible by 32).  Chosen

@@ -113,7 +113,7 @@ int run_native_worker(const NativeWorkerOpts& o, const TopoNode& node) {
   eo.dtype = bf16 ? 0 : 1;
   eo.device = o.device;
   eo.steps_per_graph = 1;
-  eo.weight_fmt = o.weight_fmt;
+  eo.weight_fmt = o.weight_fmt | CAKE_PREFILL_FMT(o.prefill_fmt);
   eo.kv_fmt = o.kv_fmt;
   char err[1024] = {0};
   void* eng = open_layers(o.model_dir.c_str(), &eo, layers.data(), (int32_t)layers.size(),

@@ -21,6 +21,7 @@ struct NativeWorkerOpts {
   bool bf16 = false;  // the reference's default dtype is f16
   int weight_fmt = 0;  // text worker: --weight-dtype (CakeEngineOpts.weight_fmt: 1 fp8, 2 mxfp4)
   int kv_fmt = 0;      // text worker: --kv-dtype (CakeEngineOpts.kv_fmt: 1 fp8) of its sessions
+  int prefill_fmt = 0; // text worker: --prefill-dtype (prefill_fmt 1: fp8 MFMA prefill)
   std::string log_tag = "cake-cli";
   // image model (run_native_sd_worker): version ("" = cake_sd.json / v1-5), resolution
   // (0 = the version's), component file overrides (unet, vae, clip, clip2)

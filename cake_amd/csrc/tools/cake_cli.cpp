@@ -113,6 +113,11 @@ const Flag kFlags[] = {
      "native Llama engine: fp8 = the KV cache as one e4m3 code per element, no scale (half the "
      "cache), chosen independently of --weight-dtype / --head-dtype (not with --parallel tp; "
      "each worker's own flag governs its own caches); model = --dtype"},
+    {"--prefill-dtype", "prefill_dtype", PyArg::kStr, "model", "model|fp8", false,
+     "native Llama engine: fp8 = the prefill projections on the fp8 matrix instruction, the "
+     "activations quantised per token to e4m3 and multiplied with the resident fp8 codes "
+     "(needs --weight-dtype fp8; not with --parallel tp; each worker's own flag governs its own "
+     "layers); model = the weights' own prefill"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -201,6 +206,8 @@ int env_int(const char* k, int def) {
 int32_t weight_fmt_of(const std::string& v) { return v == "fp8" ? 1 : (v == "mxfp4" ? 2 : 0); }
 // --kv-dtype -> CakeEngineOpts.kv_fmt (2, the test oracle, has no CLI value)
 int32_t kv_fmt_of(const std::string& v) { return v == "fp8" ? 1 : 0; }
+// --prefill-dtype -> prefill_fmt, carried in CakeEngineOpts.weight_fmt (CAKE_PREFILL_FMT)
+int32_t prefill_fmt_of(const std::string& v) { return v == "fp8" ? 1 : 0; }
 
 struct StreamCtx {
   std::string model;
@@ -310,6 +317,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
     eo.head_fmt = weight_fmt_of(o["head_dtype"].value);  // pp: ignored off rank 0; tp: refused
     eo.kv_fmt = kv_fmt_of(o["kv_dtype"].value);          // pp: this rank's caches; tp: refused
+    eo.weight_fmt |= CAKE_PREFILL_FMT(prefill_fmt_of(o["prefill_dtype"].value));  // pp: this rank
     CakePipeOpts po{rank, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
                     owners.empty() ? nullptr : owners.data(), (int32_t)owners.size()};
     CakeTPOpts to{rank, world, ctl.c_str(), 60.0, 600.0};
@@ -349,6 +357,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   eo.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
   eo.head_fmt = weight_fmt_of(o["head_dtype"].value);
   eo.kv_fmt = kv_fmt_of(o["kv_dtype"].value);
+  eo.weight_fmt |= CAKE_PREFILL_FMT(prefill_fmt_of(o["prefill_dtype"].value));
   char err[1024] = {0};
   const auto t0 = std::chrono::steady_clock::now();
   CakePipeOpts po{0, world, ctl.c_str(), o["hop_dtype"].value == "bf16" ? 1 : 0, 60.0, 600.0,
@@ -463,6 +472,7 @@ int run_native_worker(cake::PyArgs& o, const cake::TopoNode& node) {
   w.bf16 = o["dtype"].value == "bf16";
   w.weight_fmt = weight_fmt_of(o["weight_dtype"].value);
   w.kv_fmt = kv_fmt_of(o["kv_dtype"].value);
+  w.prefill_fmt = prefill_fmt_of(o["prefill_dtype"].value);
   return cake::run_native_worker(w, node);
 }
 

@@ -62,6 +62,10 @@ WEIGHT_FORMATS = {"model": 0, "fp8": 1, "mxfp4": 2}
 # CakeEngineOpts.kv_fmt ("fp8-emulated": the test oracle of "fp8", no CLI value)
 KV_FORMATS = {"model": 0, "fp8": 1, "fp8-emulated": 2}
 
+# prefill_fmt: bits 8 and up of CakeEngineOpts.weight_fmt (the 40-byte struct is full)
+PREFILL_FORMATS = {"model": 0, "fp8": 1}
+PREFILL_FMT_SHIFT = 8
+
 _lib = None
 
 
@@ -148,7 +152,7 @@ class NativeLlama:
                  seed: int = 0, worker_of: list[int] | None = None,
                  workers: list[str] | None = None, remote_timeout_s: float = 120.0,
                  weights: str = "model", head: str = "model", kv: str = "model",
-                 layers: list[int] | None = None):
+                 layers: list[int] | None = None, prefill: str = "model"):
         """world > 1: one rank of a layer-sharded pipeline, or with tp=True of a tensor-
         parallel group (rank 0 generates; the others call :meth:`serve`).  Every rank of
         one group must be constructed concurrently.  ``owners`` (pipeline): the rank of
@@ -178,6 +182,14 @@ class NativeLlama:
         "fp8" engine equals it bit for bit.  Each pipeline rank's or worker's own value
         governs its own caches.  Not available with ``tp=True`` nor with the experimental
         decode launches of docs/ENV.md.
+        ``prefill``: "model" runs prefill on the weights' own path (quantised weights are
+        widened into a 16-bit scratch before a 16-bit GEMM); "fp8" runs the four per-layer
+        prefill projections on the fp8 matrix instruction: the activation rows quantised per
+        token (e4m3fn codes, scale = amax / 448) against the resident fp8 codes, f32
+        accumulation, both scales applied to the finished sum.  Needs ``weights="fp8"`` and
+        hidden, attention and intermediate widths divisible by 128; decode, the head and the
+        KV format are unchanged.  Each pipeline rank's or worker's own value governs its own
+        layers.  Not available with ``tp=True``.
         ``layers`` (single process): open as a TCP worker's engine holding only these layers
         (no embedding, no head); drive it with :meth:`forward`."""
         if dtype not in ("bf16", "f16"):
@@ -189,13 +201,17 @@ class NativeLlama:
             raise ValueError(f"native engine head: one of {sorted(WEIGHT_FORMATS)}, got {head!r}")
         if kv not in KV_FORMATS:
             raise ValueError(f"native engine kv: one of {sorted(KV_FORMATS)}, got {kv!r}")
+        if prefill not in PREFILL_FORMATS:
+            raise ValueError(f"native engine prefill: one of {sorted(PREFILL_FORMATS)}, "
+                             f"got {prefill!r}")
+        self.prefill = prefill
         self.weights = weights
         self.head = head
         self.kv = kv
         opts = EngineOpts(int(max_seq), 0 if dtype == "bf16" else 1, int(device),
                           max(1, int(steps_per_graph)), 1 if random_init else 0,
-                          WEIGHT_FORMATS[weights], int(seed) & 0xFFFFFFFFFFFFFFFF,
-                          WEIGHT_FORMATS[head], KV_FORMATS[kv])
+                          WEIGHT_FORMATS[weights] | PREFILL_FORMATS[prefill] << PREFILL_FMT_SHIFT,
+                          int(seed) & 0xFFFFFFFFFFFFFFFF, WEIGHT_FORMATS[head], KV_FORMATS[kv])
         err = C.create_string_buffer(1024)
         self._h = None
         if world > 1 and tp:

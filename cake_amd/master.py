@@ -152,6 +152,9 @@ def _load_text(ctx):
     if getattr(ctx, "kv_dtype", "model") != "model":
         from .cli import needs_native
         raise RuntimeError(needs_native(ctx.kv_dtype, "--kv-dtype"))
+    if getattr(ctx, "prefill_dtype", "model") != "model":
+        from .cli import needs_native
+        raise RuntimeError(needs_native(ctx.prefill_dtype, "--prefill-dtype"))
     from .models.llama3.generator import LLamaGenerator
     return LLamaGenerator.load(ctx)
 

@@ -56,7 +56,8 @@ class NativeLLM(TextGenerator):
                                  dtype=_dtype_name(ctx.dtype), device=ctx.device.index or 0,
                                  weights=getattr(ctx, "weight_dtype", "model"),
                                  head=getattr(ctx, "head_dtype", "model"),
-                                 kv=getattr(ctx, "kv_dtype", "model"), **kw)
+                                 kv=getattr(ctx, "kv_dtype", "model"),
+                                 prefill=getattr(ctx, "prefill_dtype", "model"), **kw)
         tok, eos = load_tokenizer(ctx.model_path, engine.eos_ids)
         return cls(engine, tok, eos, ctx.sampling)
 

@@ -187,3 +187,10 @@ _SIGS.update({
     "cake_dequant_kv_fp8": [I, P, P, I, I, I, I, P, P, P],
     "cake_attn_decode_kv8": _SIGS["cake_attn_decode"],
 })
+# FP8 x FP8 MFMA GEMM of the quantised prefill (gemm_w8a8.hip)
+_SIGS.update({
+    "cake_gemm_w8a8": [I, I, I, P, C.c_longlong, P, P, C.c_longlong, P, P, C.c_longlong, P,
+                       C.c_longlong, I, I, I, P],
+    "cake_gemm_w8a8_plan": [I, I, I],
+    "cake_gemm_w8a8_num_cfgs": [],
+})

@@ -795,6 +795,55 @@ def dequant_rows_fp8(w8, scale, out16):
                                           _stream()), "dequant_rows_fp8")
 
 
+W8A8_EPI = {"store": 0, "resid32": 1, "swiglu": 3}
+
+
+def gemm_w8a8_num_cfgs() -> int:
+    return int(kernels().cake_gemm_w8a8_num_cfgs())
+
+
+def gemm_w8a8_plan(M: int, Nv: int, K: int) -> int:
+    """The tile shape (cfg) :func:`gemm_w8a8` takes for M tokens x Nv weight rows."""
+    return int(kernels().cake_gemm_w8a8_plan(int(M), int(Nv), int(K)))
+
+
+def gemm_w8a8(a8, sa, w8, sw, out, epi: str = "store", cfg: int = -1, dtype=None):
+    """FP8 x FP8 MFMA GEMM: ``(sa[m] * sw[n]) * sum_k fp8(a8[m, k]) * fp8(w8[n, k])``, f32
+    accumulation, the two scales applied once to the finished sum.
+
+    a8 [M, K] / w8 [Nw, K] uint8 e4m3fn codes (rows may be strided), sa [M] / sw [Nw] f32.
+    ``store``: out [M, N] 16-bit, Nw = N.  ``resid32``: out [M, N] f32, accumulated into
+    (``dtype`` names the model dtype, bf16 by default).  ``swiglu``: Nw = 2 N, gate rows
+    first, out [M, N] 16-bit = silu(gate) * up.  cfg < 0: the planner's tile shape.
+    The argument rules (K % 128, 16-byte rows and bases, ...) are the library's: a call that
+    breaks one raises KernelError (hipErrorInvalidValue) and writes nothing."""
+    if epi not in W8A8_EPI:
+        raise ValueError(f"gemm_w8a8: unknown epilogue {epi!r}")
+    for t, name in ((a8, "a8"), (w8, "w8")):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"gemm_w8a8: {name} must be uint8 [rows, K] with unit k stride")
+    M, K = a8.shape
+    Nw = w8.shape[0]
+    if w8.shape[1] != K:
+        raise ValueError("gemm_w8a8: a8 and w8 disagree on K")
+    _req(sa, "sa", dtype=torch.float32, shape=(M,))
+    _req(sw, "sw", dtype=torch.float32, shape=(Nw,))
+    N = Nw // 2 if epi == "swiglu" else Nw
+    if out.dim() != 2 or tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"gemm_w8a8: out must be [{M}, {N}] with unit column stride")
+    if epi == "resid32":
+        if out.dtype != torch.float32:
+            raise ValueError("gemm_w8a8: resid32 accumulates into an f32 out")
+        dt = _DT[dtype or torch.bfloat16]
+        c, ldc, r, ldr = None, 0, _p(out), out.stride(0)
+    else:
+        dt = _dt(out)
+        c, ldc, r, ldr = _p(out), out.stride(0), None, 0
+    check(kernels().cake_gemm_w8a8(dt, W8A8_EPI[epi], int(cfg), _p(a8), a8.stride(0), _p(sa),
+                                   _p(w8), w8.stride(0), _p(sw), c, ldc, r, ldr, M, N, K,
+                                   _stream()), "gemm_w8a8")
+
+
 def qkv_rope_w8(resid, norm_w, eps, wq, wk, wv, sq, sk, sv, inv_freq, pos, q_out, kcache, vcache,
                 kv_fmt=0):
     """:func:`qkv_rope` over fp8 weights: wq / wk / wv uint8 codes, sq / sk / sv their f32

@@ -96,6 +96,24 @@ def dequant_rows_fp8(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return codes.view(torch.float8_e4m3fn).float() * scale.float()[:, None]
 
 
+def gemm_w8a8_ref(a8: torch.Tensor, sa: torch.Tensor, w8: torch.Tensor, sw: torch.Tensor,
+                  epi: str = "store") -> torch.Tensor:
+    """float64 oracle of the FP8 x FP8 prefill GEMM (gemm_w8a8.hip), before the output's own
+    rounding: ``(sa[m] * sw[n]) * sum_k fp8(a8[m, k]) * fp8(w8[n, k])`` with the codes' exact
+    values.  ``store`` / ``resid32``: the [M, N] product (resid32 adds it to the caller's
+    residual).  ``swiglu``: w8 / sw hold 2 N rows, gate rows first; silu(gate) * up."""
+    a = a8.view(torch.float8_e4m3fn).double()
+    w = w8.view(torch.float8_e4m3fn).double()
+    y = (a @ w.T) * (sa.double()[:, None] * sw.double()[None, :])
+    if epi == "swiglu":
+        n = y.shape[1] // 2
+        g, u = y[:, :n], y[:, n:]
+        return g * torch.sigmoid(g) * u
+    if epi not in ("store", "resid32"):
+        raise ValueError(f"gemm_w8a8_ref: unknown epilogue {epi!r}")
+    return y
+
+
 MXFP4_BLOCK = 32
 # e2m1 magnitudes by code (s e e m: the sign is bit 3) and the midpoints between them
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)

@@ -362,7 +362,8 @@ def _native_rank_engine(ctx, rank: int, world: int, tp: bool):
                        hop_bf16=getattr(a, "hop_dtype", "f32") == "bf16", hop_timeout_s=timeout,
                        tp=tp, owners=owners, weights=getattr(ctx, "weight_dtype", "model"),
                        head=getattr(ctx, "head_dtype", "model"),
-                       kv=getattr(ctx, "kv_dtype", "model"))
+                       kv=getattr(ctx, "kv_dtype", "model"),
+                       prefill=getattr(ctx, "prefill_dtype", "model"))
 
 
 def _native_group(ctx) -> bool:
@@ -425,6 +426,9 @@ def run_rccl(ctx) -> None:
         if getattr(ctx, "kv_dtype", "model") != "model":
             from ..cli import needs_native
             raise RuntimeError(needs_native(ctx.kv_dtype, "--kv-dtype"))
+        if getattr(ctx, "prefill_dtype", "model") != "model":
+            from ..cli import needs_native
+            raise RuntimeError(needs_native(ctx.prefill_dtype, "--prefill-dtype"))
         ctx.args.hop = "dist"  # the fallback transport: RCCL p2p / all-reduce
         ctx.args.allreduce = "dist"
     if getattr(ctx.args, "parallel", "pp") == "tp":
