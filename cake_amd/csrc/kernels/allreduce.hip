@@ -15,6 +15,11 @@
 //   sums them with its own partial.  On an 8-GPU MI355X node every pair of GPUs
 //   has its own xGMI link, so the N-1 pushes go out in parallel.
 //
+// The sum runs in ascending rank order on every rank, (((p0 + p1) + p2) + ...),
+// with the rank's own partial taken at its rank's position: f32 addition is not
+// associative, and this way every rank holds a bit-identical result (the
+// residual streams are replicas, not merely close).
+//
 // The tag is a per-rank device counter advanced by the last workgroup to finish
 // (agent-scope ticket), so graph replays stay in lock step; the inbox has two
 // parity banks, so a fast rank's next all-reduce cannot overwrite words a slow
@@ -91,12 +96,15 @@ __global__ __launch_bounds__(kArThreads) void ar_sum_kernel(ArArgs a, const floa
   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
   bool late = false;
   for (int i = i0; i < a.n; i += stride) {
-    float s = partial[i];
+    // ascending rank order on every rank, the own partial at its rank's position
+    const float own = partial[i];
+    float s = 0.0f;
     for (int r = 0; r < a.world; ++r) {
-      if (r == a.rank) continue;
-      const unsigned long long g = ar_poll(a.inbox + bank + (size_t)r * a.n + i, tag, t0,
-                                           a.timeout_ticks, late);
-      s += __uint_as_float((uint32_t)g);
+      float v = own;
+      if (r != a.rank)
+        v = __uint_as_float((uint32_t)ar_poll(a.inbox + bank + (size_t)r * a.n + i, tag, t0,
+                                              a.timeout_ticks, late));
+      s = r == 0 ? v : s + v;  // (not 0 + v: a sum of -0.0 stays -0.0)
     }
     if constexpr (ACC) out[i] += s;
     else out[i] = s;
