@@ -1782,11 +1782,19 @@ class Llama {
 
  private:
 
-  // decode attention of local layer l over the fp8 code cache (kv_fmt 1)
-  void attn_kv8(int l) {
+  // decode attention of local layer l into attn_out_: over the fp8 code cache (kv_fmt 1),
+  // head-parallel for a short context, split over the context otherwise
+  void attn(int l) {
     const Cfg& c = lc_;
-    k_check(cake_attn_decode_kv8(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                                 part_, tickets_, attn_out_, st_), "attn_decode_kv8");
+    if (kvfmt_ == 1)
+      k_check(cake_attn_decode_kv8(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
+                                   part_, tickets_, attn_out_, st_), "attn_decode_kv8");
+    else if (short_step_)
+      k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
+                                     scale(), attn_out_, st_), "attn_heads");
+    else
+      k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
+                               part_, tickets_, attn_out_, st_), "attn_decode");
   }
 
   void step_layers(const std::vector<int>* sel = nullptr) {
@@ -1804,14 +1812,7 @@ class Llama {
                                      w.eqkv + (size_t)(nq + nk) * re, c.H, c.nh, c.nkv, c.hd,
                                      inv_freq_, pos_, q_, kc(l), vc(l), S_, st_, kvfmt_),
                 "qkv_rope_w4");
-        if (kvfmt_ == 1)
-          attn_kv8(l);
-        else if (short_step_)  // head-parallel short-context attention
-          k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
-                                         scale(), attn_out_, st_), "attn_heads");
-        else
-          k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                                   part_, tickets_, attn_out_, st_), "attn_decode");
+        attn(l);
         k_check(cake_gemv_x16_w4(dt_, attn_out_, w.wo, w.eo, nq, c.H, resid_, 1, st_), "o_proj_w4");
         const uint8_t* gu4 = reinterpret_cast<const uint8_t*>(w.wgu);
         k_check(cake_swiglu_w4(dt_, resid_, w.ln2, (float)c.eps, gu4, gu4 + (size_t)c.I * rb,
@@ -1825,14 +1826,7 @@ class Llama {
                                      q8 + (size_t)(nq + nk) * c.H, w.sqkv, w.sqkv + nq,
                                      w.sqkv + nq + nk, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
                                      kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope_w8");
-        if (kvfmt_ == 1)
-          attn_kv8(l);
-        else if (short_step_)  // head-parallel short-context attention
-          k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
-                                         scale(), attn_out_, st_), "attn_heads");
-        else
-          k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                                   part_, tickets_, attn_out_, st_), "attn_decode");
+        attn(l);
         k_check(cake_gemv_x16_w8(dt_, attn_out_, w.wo, w.so, nq, c.H, resid_, 1, st_), "o_proj_w8");
         const uint8_t* gu8 = reinterpret_cast<const uint8_t*>(w.wgu);
         k_check(cake_swiglu_w8(dt_, resid_, w.ln2, (float)c.eps, gu8, gu8 + (size_t)c.I * c.H,
@@ -1844,21 +1838,13 @@ class Llama {
       k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
                                 wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
                                 pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
-      if (kvfmt_ == 1) {  // fp8 cache: core 2's split launch over the codes (tp_ == 1)
-        attn_kv8(l);
-        k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, resid_, 1, st_), "o_proj");
-      } else if (short_step_ && ao_ok_) {  // one split: attention + o_proj in one launch
+      if (kvfmt_ != 1 && short_step_ && ao_ok_) {  // one split: attention + o_proj in one launch
         k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.wo,
                                 nq, c.H, tp_ > 1 ? partial_ : resid_, tp_ > 1 ? 0 : 1, ao_ws_,
                                 ao_tickets_, tickets_ + 2 * c.nkv, st_), "attn_oproj");
         if (tp_ > 1) ar_sum();
-      } else {
-        if (short_step_)  // head-parallel short-context attention
-          k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
-                                         scale(), attn_out_, st_), "attn_heads");
-        else
-          k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                                 part_, tickets_, attn_out_, st_), "attn_decode");
+      } else {  // (the fp8 cache runs with tp_ == 1)
+        attn(l);
         if (tp_ > 1) {
           k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, partial_, 0, st_), "o_proj");
           ar_sum();

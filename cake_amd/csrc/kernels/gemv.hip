@@ -26,37 +26,44 @@
 #include "gemv_kernel.h"
 
 namespace cake {
-GemvTune g_tune[kNumKinds] = {{2, 4, 1024}, {2, 4, 512}, {4, 4, 1024}, {4, 4, 256},
-                                     {4, 4, 1024}};
-
+GemvTune g_tune[3][kNumKinds] = {
+    // W16.  Measured in the decode graph (8B, tok/s):
+    // profiles/r2_gemv_split_prologue_sweep*.jsonl — prefetching the first weight rows
+    // behind the split x prologue is +10% (323 -> 357); the round-3 re-sweep
+    // (profiles/r3_decode_gemv_tuning_ingraph.jsonl) moved QKV to U 2 / PF 4 (+0.3 %, every
+    // round) and left the rest
+    {{2, 4, 1024}, {2, 4, 512}, {4, 4, 1024}, {4, 4, 256}, {4, 4, 1024}},
+    // W8: the whole 4096-byte row of an 8B projection in the prefetch registers; measured in
+    // the 8B decode graph, one kind varied at a time
+    // (profiles/fp8_decode_tuning_sweep.jsonl): SwiGLU at a 1024-block cap is -3..-5 %
+    // ms/token against the 16-bit twin's 512 (rows are half as long, so a wave's fixed
+    // prologue weighs twice as much per pair); every other variation stayed inside the 2 %
+    // engine-to-engine spread of that sweep.  The fourth kind is the quantised lm_head,
+    // started from the SwiGLU values
+    {{2, 4, 1024}, {2, 4, 1024}, {4, 4, 1024}, {2, 4, 1024}},
+    // W4: PF 4 runs as the deepest prefetch the row fills (W4::prefetch): the whole row of a
+    // hidden-width projection at 8B (2 chunks per lane) and at 70B (4).  Measured in the 8B
+    // decode graph, one kind varied at a time (profiles/mxfp4_decode_tuning_sweep.jsonl):
+    // the prefetch is worth 4-8 % ms/token per kind, the SwiGLU cap of 1024 beats 512 and
+    // 2048; every other variation stayed under twice the 1.2 % spread of the default (x16
+    // at U = 1 was -1.4 to -2 %) and was not adopted.  Nothing was swept at 70B.  The fourth
+    // kind is the quantised lm_head, started from the SwiGLU values.
+    {{2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}}};
 }  // namespace cake
 
 CAKE_API int cake_gemv_set_tuning(int kind, int U, int prefetch, int max_blocks) {
-  if (kind < 0 || kind >= kNumKinds || (U != 2 && U != 4 && U != 8) || max_blocks < 1 ||
-      (prefetch != 0 && prefetch != 4 && prefetch != 8))
-    return (int)hipErrorInvalidValue;
-  g_tune[kind] = GemvTune{U, prefetch, max_blocks};
-  return 0;
+  return gemv_set_tuning<W16>(kind, U, prefetch, max_blocks);
 }
 
-// kv_fmt (common.h KvFmt): 0 = 16-bit cache rows, 1 = kcache / vcache hold one e4m3fn code
-// per element (quant_kv_fp8 of the f32 roped K / f32 V), 2 = those codes' values as 16 bits
 CAKE_API int cake_qkv_rope_kvf(int dt, const float* resid, const void* norm_w, float eps,
                                const void* wq, const void* wk, const void* wv, int K, int nh,
                                int nkv, int hd, const float* inv_freq, const int* pos,
                                float* q_out, void* kcache, void* vcache, int S,
                                hipStream_t st, int kv_fmt) {
-  if (K % 8 || hd % 2 || kv_fmt < 0 || kv_fmt > 2) return (int)hipErrorInvalidValue;
-  QkvArgs a{resid, (const uint16_t*)norm_w, eps, (const uint16_t*)wq,
-            (const uint16_t*)wk, (const uint16_t*)wv, K, nh, nkv, hd, inv_freq, pos,
-            q_out, (uint16_t*)kcache, (uint16_t*)vcache, S, kv_fmt};
-  const int npairs = (nh + 2 * nkv) * (hd / 2);
-  const size_t lds = (size_t)K * sizeof(float);
-  const GemvTune t = g_tune[kQkv];
-  DISPATCH_DT(dt, DISPATCH_TUNE(t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((qkv_rope_kernel<DT, U, PF, NX>),
-                                                      dim3(grid_for(npairs, t.MB)),
-                                                      dim3(kGemvThreads), lds, st, a))));
-  return (int)hipGetLastError();
+  return launch_qkv<W16>(dt, {resid, (const uint16_t*)norm_w, eps, {(const uint16_t*)wq},
+                              {(const uint16_t*)wk}, {(const uint16_t*)wv}, K, nh, nkv, hd,
+                              inv_freq, pos, q_out, (uint16_t*)kcache, (uint16_t*)vcache, S,
+                              kv_fmt}, st);
 }
 
 CAKE_API int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float eps,
@@ -67,5 +74,3 @@ CAKE_API int cake_qkv_rope(int dt, const float* resid, const void* norm_w, float
   return cake_qkv_rope_kvf(dt, resid, norm_w, eps, wq, wk, wv, K, nh, nkv, hd, inv_freq, pos,
                            q_out, kcache, vcache, S, st, 0);
 }
-
-

@@ -1,6 +1,8 @@
-// Decode GEMV kernels (shared by gemv.hip, gemv_mlp.hip, gemv_head.hip: the launchers
-// are split across translation units so their many (dtype, U, prefetch, NX)
-// instantiations compile in parallel).  Design notes: gemv.hip.
+// Decode GEMV kernels and their launchers: one kernel family over a weight-format policy F
+// (W16 below, W8 in gemv_w8_kernel.h, W4 in gemv_w4_kernel.h).  The C entry points are
+// spread over gemv*.hip so the many (format, dtype, U, prefetch, NX) instantiations compile
+// in parallel.  Design notes: gemv.hip.  One (kind, format) is not of the family: the MXFP4
+// 16-bit-input GEMV keeps its own kernel and pair loop (gemv_w4_x16.hip says why).
 #pragma once
 #include "common.h"
 
@@ -10,12 +12,128 @@ constexpr int kGemvThreads = 256;  // 4 waves
 constexpr int kGemvWaves = kGemvThreads / 64;
 constexpr int kGemvMaxBlocks = 1024;
 
+typedef float f32x2_t __attribute__((ext_vector_type(2)));  // as mxfp4.h
+
+// Launch geometry per kernel kind (tunable at run time; defaults from the
+// rocprofv3-measured sweeps in profiles/): U = chunks in flight per row,
+// PF = prefetch the first weight batch before the x prologue, MB = grid cap.
+struct GemvTune { int U, PF, MB; };
+// kX16 = 16-bit-input GEMVs (W16: those with K > 8192, down_proj), kX16S = W16 with
+// K <= 8192 (o_proj); the quantised formats have the first four kinds
+enum GemvKind { kQkv = 0, kSwiglu = 1, kX16 = 2, kNormF32 = 3, kX16S = 4, kNumKinds = 5 };
+// the run-time tuning tables [F::kFmt][kind] (defined in gemv.hip, set by cake_gemv*_set_tuning)
+extern GemvTune g_tune[3][kNumKinds];
+
+// ---------------------------------------------------------------------------
+// Weight formats.  A policy F supplies what differs between the formats:
+//   kFmt, kKinds          its row of g_tune and how many kinds of it exist
+//   kLog2                 log2 of the k values in a lane's 16-byte chunk
+//   kPad32, kPad16        the LDS x row (f32 / 16-bit) holds K rounded up to this many values
+//   perm32(i), perm16(i)  where value i of the f32 / 16-bit x row sits in LDS
+//   kU[3], kPF[2]         the U values and the non-zero prefetch depths (deepest first) that are
+//                         instantiated: what *_set_tuning accepts (besides prefetch 0)
+//   prefetch(pf, K)       the prefetch depth a row of K values runs with
+//   kStrict               launchers refuse K < one chunk and empty outputs
+//   Acc, zero(), total()  a row's per-lane accumulator, and its sum before wave_sum
+//   Mat, pick()           the matrix handle (a kernel argument) and the QKV matrix of a pair
+//   kRowScale             Mat has one f32 `scale` per row, applied to the wave sums
+//   Rows, rows()          the pair of rows a wave works on
+//   Chunk, load<NT>()     one chunk of both rows (NT: non-temporal, the main loop)
+//   fma<DT, XF32>()       acc += chunk . x
+// ---------------------------------------------------------------------------
+
+// the q / k / v pointer of pair kind 0 / 1 / 2 by address arithmetic, not a pointer select:
+// a select between kernel-argument fields becomes a memory load of the argument block, which
+// would stand (in vmcnt order) in front of the split prologue's x loads (offsets from q keep
+// the global address space visible: no flat loads)
+template <class T>
+__device__ __forceinline__ const T* pick3(const T* q, const T* k, const T* v, int kind) {
+  const ptrdiff_t dk = k - q, dv = v - q;  // both read ahead of the select
+  return q + (kind == 0 ? 0 : (kind == 1 ? dk : dv));
+}
+
+// rows of 16-byte chunks with nothing beside them (W16, W8)
+struct PlainRows {
+  struct Rows { const uint4 *a, *b; };
+  struct Chunk { uint4 a, b; };
+  template <bool NT> static __device__ __forceinline__ Chunk load(const Rows& r, int c) {
+    if constexpr (NT) return {ld_nt16(r.a + c), ld_nt16(r.b + c)};
+    else return {r.a[c], r.b[c]};
+  }
+  // PF falls back to 0 when a row is shorter than PF*64 chunks (small test shapes)
+  template <int LOG2> static int prefetch_if_filled(int pf, int K) {
+    return (K >> LOG2) >= 64 * pf ? pf : 0;
+  }
+};
+
+template <int DT, bool XF32>
+__device__ __forceinline__ void load_x8(const void* xs, int chunk, float* o) {
+  if constexpr (XF32) {
+    const float4* p = reinterpret_cast<const float4*>(xs) + chunk * 2;
+    const float4 a = p[0], b = p[1];
+    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
+    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
+  } else {
+    unpack8<DT>(reinterpret_cast<const uint4*>(xs)[chunk], o);
+  }
+}
+
+// 16-bit weights [N, K]: 8 k values per chunk, a scalar fmaf chain per row
+struct W16 : PlainRows {
+  static constexpr int kFmt = 0, kKinds = kNumKinds, kLog2 = 3, kPad32 = 1, kPad16 = 1;
+  static constexpr int kU[3] = {2, 4, 8}, kPF[2] = {8, 4};
+  static constexpr bool kStrict = false, kRowScale = false;
+  static __device__ __forceinline__ int perm32(int i) { return i; }
+  static __device__ __forceinline__ int perm16(int i) { return i; }
+  static int prefetch(int pf, int K) { return prefetch_if_filled<kLog2>(pf, K); }
+  using Acc = float;
+  static __device__ __forceinline__ Acc zero() { return 0.f; }
+  static __device__ __forceinline__ float total(Acc a) { return a; }
+  struct Mat { const uint16_t* w; };
+  static __device__ __forceinline__ Mat pick(const Mat& q, const Mat& k, const Mat& v, int kind) {
+    return {pick3(q.w, k.w, v.w, kind)};
+  }
+  static __device__ __forceinline__ Rows rows(const Mat& ma, size_t ra, const Mat& mb, size_t rb,
+                                              int K) {
+    return {reinterpret_cast<const uint4*>(ma.w + ra * K),
+            reinterpret_cast<const uint4*>(mb.w + rb * K)};
+  }
+  template <int DT, bool XF32>
+  static __device__ __forceinline__ void fma(const void* xs, int chunk, const Chunk& v, Acc& acc_a,
+                                             Acc& acc_b) {
+    float xv[8], fa[8], fb[8];
+    load_x8<DT, XF32>(xs, chunk, xv);
+    unpack8<DT>(v.a, fa);
+    unpack8<DT>(v.b, fb);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      acc_a = fmaf(fa[e], xv[e], acc_a);
+      acc_b = fmaf(fb[e], xv[e], acc_b);
+    }
+  }
+};
+
+// The epilogue scale hook.  kRowScale (fp8): the first pair's row scales are requested in
+// the prologue slot (row_scale) and every wave sum is multiplied by its row's (descale);
+// nothing for the other formats.
+template <class F>
+__device__ __forceinline__ float row_scale(const typename F::Mat& m, size_t row) {
+  if constexpr (F::kRowScale) return m.scale[row];
+  else return 1.f;
+}
+template <class F>
+__device__ __forceinline__ float descale(float d, bool first, float s0, const typename F::Mat& m,
+                                         size_t row) {
+  if constexpr (F::kRowScale) return d * (first ? s0 : m.scale[row]);
+  else return d;
+}
+
 // ---------------------------------------------------------------------------
 // x staging (prologues)
 // ---------------------------------------------------------------------------
 
 // Normalise a f32 row into LDS:  xs[i] = x[i] * rsqrt(mean(x^2) + eps) * w[i].
-template <int DT>
+template <class F, int DT>
 __device__ __forceinline__ void stage_rmsnorm(const float* __restrict__ x,
                                               const uint16_t* __restrict__ w,
                                               float eps, int K, float* xs) {
@@ -23,28 +141,29 @@ __device__ __forceinline__ void stage_rmsnorm(const float* __restrict__ x,
   float ss = 0.f;
   for (int i = threadIdx.x * 4; i < K; i += kGemvThreads * 4) {
     const float4 v = *reinterpret_cast<const float4*>(x + i);
-    *reinterpret_cast<float4*>(xs + i) = v;
+    *reinterpret_cast<float4*>(xs + F::perm32(i)) = v;
     ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
   }
   ss = block_sum(ss, red);
   const float r = rsqrtf(ss / (float)K + eps);
   for (int i = threadIdx.x * 4; i < K; i += kGemvThreads * 4) {
-    float4 v = *reinterpret_cast<float4*>(xs + i);
+    float4 v = *reinterpret_cast<float4*>(xs + F::perm32(i));
     const uint2 wv = *reinterpret_cast<const uint2*>(w + i);
     v.x *= r * to_f32<DT>((uint16_t)(wv.x & 0xffff));
     v.y *= r * to_f32<DT>((uint16_t)(wv.x >> 16));
     v.z *= r * to_f32<DT>((uint16_t)(wv.y & 0xffff));
     v.w *= r * to_f32<DT>((uint16_t)(wv.y >> 16));
-    *reinterpret_cast<float4*>(xs + i) = v;
+    *reinterpret_cast<float4*>(xs + F::perm32(i)) = v;
   }
   __syncthreads();
 }
 
 // Copy a 16-bit activation row into LDS (kept 16-bit: 70B down_proj has K=28672).
+template <class F>
 __device__ __forceinline__ void stage_plain16(const uint16_t* __restrict__ x, int K,
                                               uint16_t* xs) {
   for (int i = threadIdx.x * 8; i < K; i += kGemvThreads * 8)
-    *reinterpret_cast<uint4*>(xs + i) = *reinterpret_cast<const uint4*>(x + i);
+    *reinterpret_cast<uint4*>(xs + F::perm16(i)) = *reinterpret_cast<const uint4*>(x + i);
   __syncthreads();
 }
 
@@ -54,7 +173,7 @@ __device__ __forceinline__ void stage_plain16(const uint16_t* __restrict__ x, in
 // plain prologue order — made the norm wait for the whole weight batch; in this
 // order the norm waits only for x, and its reduction / LDS round trips overlap
 // the weight stream.  K = 1024 NX (RMSNorm, f32 row) or 2048 NX (16-bit row).
-template <int DT, int NX> struct NormPre {  // K <= 1024 NX, K % 4 == 0
+template <class F, int DT, int NX> struct NormPre {  // K <= 1024 NX, K % 4 == 0
   float4 x[NX];
   uint2 w[NX];
   __device__ __forceinline__ void load(const float* __restrict__ xg, const uint16_t* __restrict__ wg,
@@ -81,13 +200,13 @@ template <int DT, int NX> struct NormPre {  // K <= 1024 NX, K % 4 == 0
       v.y *= r * to_f32<DT>((uint16_t)(w[j].x >> 16));
       v.z *= r * to_f32<DT>((uint16_t)(w[j].y & 0xffff));
       v.w *= r * to_f32<DT>((uint16_t)(w[j].y >> 16));
-      if (i < K) *reinterpret_cast<float4*>(xs + i) = v;
+      if (i < K) *reinterpret_cast<float4*>(xs + F::perm32(i)) = v;
     }
     __syncthreads();
   }
 };
 
-template <int NX> struct Plain16Pre {  // K <= 2048 NX, K % 8 == 0
+template <class F, int NX> struct Plain16Pre {  // K <= 2048 NX, K % 8 == 0
   uint4 v[NX];
   __device__ __forceinline__ void load(const uint16_t* __restrict__ xg, int K) {
 #pragma unroll
@@ -100,128 +219,91 @@ template <int NX> struct Plain16Pre {  // K <= 2048 NX, K % 8 == 0
 #pragma unroll
     for (int j = 0; j < NX; ++j) {
       const int i = (j * kGemvThreads + threadIdx.x) * 8;
-      if (i < K) *reinterpret_cast<uint4*>(xs + i) = v[j];
+      if (i < K) *reinterpret_cast<uint4*>(xs + F::perm16(i)) = v[j];
     }
     __syncthreads();
   }
 };
-
-template <int DT, bool XF32>
-__device__ __forceinline__ void load_x8(const void* xs, int chunk, float* o) {
-  if constexpr (XF32) {
-    const float4* p = reinterpret_cast<const float4*>(xs) + chunk * 2;
-    const float4 a = p[0], b = p[1];
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w;
-    o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-  } else {
-    unpack8<DT>(reinterpret_cast<const uint4*>(xs)[chunk], o);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // core: one wave computes dot products of a PAIR of weight rows with the x row
 // staged in LDS.  U = 16-byte chunks per row in flight per lane per iteration
 // (2*U loads outstanding).  PFC = chunks per row per lane of the wave's FIRST
 // pair issued before the x prologue (RMSNorm / staging) so the HBM stream
-// overlaps it; for K = 4096 PFC = 8 is the whole pair (64 VGPRs).  All
+// overlaps it; for 16-bit K = 4096 PFC = 8 is the whole pair (64 VGPRs).  All
 // register arrays are indexed by compile-time constants (no scratch).
 // ---------------------------------------------------------------------------
-template <int DT, bool XF32>
-__device__ __forceinline__ void fma_chunk(const void* xs, int chunk, const uint4 va,
-                                          const uint4 vb, float& acc_a, float& acc_b) {
-  float xv[8], fa[8], fb[8];
-  load_x8<DT, XF32>(xs, chunk, xv);
-  unpack8<DT>(va, fa);
-  unpack8<DT>(vb, fb);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    acc_a = fmaf(fa[e], xv[e], acc_a);
-    acc_b = fmaf(fb[e], xv[e], acc_b);
-  }
-}
 
-// accumulate chunks [c_start, nch) of rows wa, wb
-template <int DT, bool XF32, int U>
-__device__ __forceinline__ void dot_range(const uint16_t* __restrict__ wa,
-                                          const uint16_t* __restrict__ wb, const void* xs,
-                                          int nch, int c_start, float& acc_a, float& acc_b) {
+// accumulate chunks [c_start, nch) of the pair (c_start a multiple of 64)
+template <class F, int DT, bool XF32, int U>
+__device__ __forceinline__ void dot_range(const typename F::Rows& r, const void* xs, int nch,
+                                          int c_start, typename F::Acc& acc_a,
+                                          typename F::Acc& acc_b) {
   const int lane = threadIdx.x & 63;
-  const uint4* a4 = reinterpret_cast<const uint4*>(wa);
-  const uint4* b4 = reinterpret_cast<const uint4*>(wb);
   const int full = c_start + ((nch - c_start) / (64 * U)) * (64 * U);
   for (int c0 = c_start; c0 < full; c0 += 64 * U) {
-    uint4 va[U], vb[U];
+    typename F::Chunk v[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      va[u] = ld_nt16(a4 + c0 + u * 64 + lane);
-      vb[u] = ld_nt16(b4 + c0 + u * 64 + lane);
-    }
+    for (int u = 0; u < U; ++u) v[u] = F::template load<true>(r, c0 + u * 64 + lane);
 #pragma unroll
-    for (int u = 0; u < U; ++u) fma_chunk<DT, XF32>(xs, c0 + u * 64 + lane, va[u], vb[u], acc_a, acc_b);
+    for (int u = 0; u < U; ++u) F::template fma<DT, XF32>(xs, c0 + u * 64 + lane, v[u], acc_a, acc_b);
   }
-  for (int c = full + lane; c < nch; c += 64) fma_chunk<DT, XF32>(xs, c, a4[c], b4[c], acc_a, acc_b);
+  // the tail: lanes past nch have no chunk
+  for (int c = full + lane; c < nch; c += 64)
+    F::template fma<DT, XF32>(xs, c, F::template load<false>(r, c), acc_a, acc_b);
 }
 
-template <int N> struct Regs { uint4 a[N], b[N]; };
-template <> struct Regs<0> { uint4 a[1], b[1]; };
+// prefetch registers: PFC chunks of the pair per lane
+template <class F, int PFC> struct Regs { typename F::Chunk c[PFC > 0 ? PFC : 1]; };
 
-// issue the first PFC chunks of (wa, wb)
-template <int PFC>
-__device__ __forceinline__ void prefetch_rows(const uint16_t* wa, const uint16_t* wb, Regs<PFC>& r) {
+// issue the first PFC chunks of the pair (nch >= 64 PFC)
+template <class F, int PFC>
+__device__ __forceinline__ void prefetch_rows(const typename F::Rows& r, Regs<F, PFC>& g) {
   if constexpr (PFC > 0) {
     const int lane = threadIdx.x & 63;
-    const uint4* a4 = reinterpret_cast<const uint4*>(wa);
-    const uint4* b4 = reinterpret_cast<const uint4*>(wb);
 #pragma unroll
-    for (int c = 0; c < PFC; ++c) {
-      r.a[c] = ld_nt16(a4 + c * 64 + lane);
-      r.b[c] = ld_nt16(b4 + c * 64 + lane);
-    }
+    for (int c = 0; c < PFC; ++c) g.c[c] = F::template load<true>(r, c * 64 + lane);
   }
 }
 
-// Walk the wave's pairs p0, p0+stride, ...: map(p, wa, wb) gives the rows,
-// epi(p, da, db) consumes the two dot products (full wave sums).
-template <int DT, bool XF32, int U, int PFC, class Map, class Epi>
+// Walk the wave's pairs p0, p0+stride, ...: map(p) gives the rows, epi(p, da, db)
+// consumes the two dot products (full wave sums; kRowScale: not yet scaled).
+template <class F, int DT, bool XF32, int U, int PFC, class Map, class Epi>
 __device__ __forceinline__ void run_pairs(const Map& map, const Epi& epi, const void* xs, int K,
-                                          int npairs, int p0, int stride, const Regs<PFC>& pre) {
-  const int nch = K >> 3;
+                                          int npairs, int p0, int stride,
+                                          const Regs<F, PFC>& pre) {
+  const int nch = K >> F::kLog2;
   int p = p0;
   if constexpr (PFC > 0) {
     // Unconditional (an idle wave works on a clamped pair and drops it): a use of
     // the prefetched registers inside a branch lets the compiler sink the
     // prefetch loads past the x prologue's barrier, serialising them again.
-    const uint16_t *wa, *wb;
-    map(p < npairs ? p : npairs - 1, wa, wb);
+    const typename F::Rows r = map(p < npairs ? p : npairs - 1);
     const int lane = threadIdx.x & 63;
-    float aa = 0.f, ab = 0.f;
+    typename F::Acc aa = F::zero(), ab = F::zero();
 #pragma unroll
-    for (int c = 0; c < PFC; ++c) fma_chunk<DT, XF32>(xs, c * 64 + lane, pre.a[c], pre.b[c], aa, ab);
-    dot_range<DT, XF32, U>(wa, wb, xs, nch, PFC * 64, aa, ab);
-    aa = wave_sum(aa);
-    ab = wave_sum(ab);
-    if (p < npairs) epi(p, aa, ab);
+    for (int c = 0; c < PFC; ++c) F::template fma<DT, XF32>(xs, c * 64 + lane, pre.c[c], aa, ab);
+    dot_range<F, DT, XF32, U>(r, xs, nch, PFC * 64, aa, ab);
+    const float sa = wave_sum(F::total(aa)), sb = wave_sum(F::total(ab));
+    if (p < npairs) epi(p, sa, sb);
     p += stride;
   }
   for (; p < npairs; p += stride) {
-    const uint16_t *wa, *wb;
-    map(p, wa, wb);
-    float aa = 0.f, ab = 0.f;
-    dot_range<DT, XF32, U>(wa, wb, xs, nch, 0, aa, ab);
-    epi(p, wave_sum(aa), wave_sum(ab));
+    const typename F::Rows r = map(p);
+    typename F::Acc aa = F::zero(), ab = F::zero();
+    dot_range<F, DT, XF32, U>(r, xs, nch, 0, aa, ab);
+    epi(p, wave_sum(F::total(aa)), wave_sum(F::total(ab)));
   }
 }
 
 // ---------------------------------------------------------------------------
 // QKV + RoPE + KV-cache write
 // ---------------------------------------------------------------------------
-struct QkvArgs {
+template <class F> struct QkvArgs {
   const float* resid;      // [K] f32
   const uint16_t* norm_w;  // [K]
   float eps;
-  const uint16_t* wq;  // [nh*hd, K]
-  const uint16_t* wk;  // [nkv*hd, K]
-  const uint16_t* wv;  // [nkv*hd, K]
+  typename F::Mat q, k, v;  // [nh*hd, K], [nkv*hd, K], [nkv*hd, K]
   int K, nh, nkv, hd;
   const float* inv_freq;  // [hd/2]
   const int* pos;         // device scalar: position of this token
@@ -232,65 +314,64 @@ struct QkvArgs {
   int kv_fmt;             // KvFmt of the cache (common.h); 1: kcache / vcache hold bytes
 };
 
-struct QkvRow {
-  const uint16_t* base;
-  int kind, head, i;  // kind 0=q 1=k 2=v
+// pair p of the fused projection: rows (ra, ra + hd/2) of head `head` of its matrix
+struct QkvPair {
+  int kind, head, i;  // kind 0 = q, 1 = k, 2 = v; i = the pair's RoPE frequency
   size_t ra;
 };
 
-__device__ __forceinline__ QkvRow qkv_row(const QkvArgs& a, int p) {
-  const int half = a.hd >> 1;
+__device__ __forceinline__ QkvPair qkv_pair(int p, int half, int nh, int nqk, int hd) {
   const int slot = p / half;
-  QkvRow r;
+  const bool isq = slot < nh, isk = !isq && slot < nqk;
+  QkvPair r;
+  r.kind = isq ? 0 : (isk ? 1 : 2);
+  r.head = slot - (isq ? 0 : (isk ? nh : nqk));
   r.i = p - slot * half;
-  if (slot < a.nh) { r.kind = 0; r.head = slot; r.base = a.wq; }
-  else if (slot < a.nh + a.nkv) { r.kind = 1; r.head = slot - a.nh; r.base = a.wk; }
-  else { r.kind = 2; r.head = slot - a.nh - a.nkv; r.base = a.wv; }
-  r.ra = (size_t)r.head * a.hd + r.i;
+  r.ra = (size_t)r.head * hd + r.i;
   return r;
 }
 
-template <int DT, int U, int PFC, int NX>
-__global__ __launch_bounds__(kGemvThreads) void qkv_rope_kernel(QkvArgs a) {
+template <class F, int DT, int U, int PFC, int NX>
+__global__ __launch_bounds__(kGemvThreads) void qkv_rope_kernel(QkvArgs<F> a) {
   extern __shared__ float xs[];
   const int half = a.hd >> 1;
   const int npairs = (a.nh + 2 * a.nkv) * half;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int p0 = blockIdx.x * kGemvWaves + wave;
-  // base selected by address arithmetic, not a pointer select: a select between
-  // kernel-argument fields becomes a memory load of the argument block, which
-  // would stand (in vmcnt order) in front of the split prologue's x loads
-  // (offsets from wq keep the global address space visible: no flat loads)
-  const uint16_t* wq = a.wq;
-  const ptrdiff_t dk = a.wk - a.wq, dv = a.wv - a.wq;
   const int nh = a.nh, nqk = a.nh + a.nkv, hd = a.hd, K = a.K;
-  auto map = [=](int p, const uint16_t*& wa, const uint16_t*& wb) {
-    const int slot = p / half;
-    const bool isq = slot < nh, isk = !isq && slot < nqk;
-    const uint16_t* base = wq + (isq ? 0 : (isk ? dk : dv));
-    const int head = slot - (isq ? 0 : (isk ? nh : nqk));
-    const size_t ra = (size_t)head * hd + (p - slot * half);
-    wa = base + ra * K;
-    wb = base + (ra + half) * K;
+  auto map = [&](int p) {
+    const QkvPair r = qkv_pair(p, half, nh, nqk, hd);
+    const typename F::Mat m = F::pick(a.q, a.k, a.v, r.kind);  // by address arithmetic: pick3
+    return F::rows(m, r.ra, m, r.ra + half, K);
   };
-  Regs<PFC> pre;
-  NormPre<DT, NX> xp;
-  const uint16_t *wa0, *wb0;  // rows first: their address math may load (kernarg select)
-  map(p0 < npairs ? p0 : npairs - 1, wa0, wb0);
+  Regs<F, PFC> pre;
+  NormPre<F, DT, NX> xp;
+  const int pc = p0 < npairs ? p0 : npairs - 1;
+  const typename F::Rows r0 = map(pc);  // rows first: their address math may load (kernarg select)
   if constexpr (NX > 0) xp.load(a.resid, a.norm_w, a.K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
-  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<PFC>(wa0, wb0, pre);  // NX: exact vmcnt
-  // the RoPE frequency of the wave's first pair, requested now: loaded in the
-  // epilogue it was one more memory round trip at the end of every wave
-  const int pc = p0 < npairs ? p0 : npairs - 1;
-  const float f0 = a.inv_freq[pc - (pc / half) * half];
+  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
+  // the epilogue operands of the wave's first pair, requested now: the RoPE frequency
+  // (loaded in the epilogue it was one more memory round trip at the end of every wave)
+  // and the row scales
+  const QkvPair rc = qkv_pair(pc, half, nh, nqk, hd);
+  const float f0 = a.inv_freq[rc.i];
+  const typename F::Mat mc = F::pick(a.q, a.k, a.v, rc.kind);
+  const float s0a = row_scale<F>(mc, rc.ra), s0b = row_scale<F>(mc, rc.ra + half);
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (NX > 0) xp.finish(a.eps, a.K, xs);
-  else stage_rmsnorm<DT>(a.resid, a.norm_w, a.eps, a.K, xs);
+  else stage_rmsnorm<F, DT>(a.resid, a.norm_w, a.eps, a.K, xs);
   const int pos = *a.pos;
   auto epi = [&](int p, float da, float db) {
     if (lane != 0) return;
-    const QkvRow r = qkv_row(a, p);
+    const QkvPair r = qkv_pair(p, half, nh, nqk, hd);
+    const typename F::Mat m = F::pick(a.q, a.k, a.v, r.kind);
+    if constexpr (F::kRowScale) {
+      float sa = s0a, sb = s0b;
+      if (p != p0) { sa = m.scale[r.ra]; sb = m.scale[r.ra + half]; }
+      da *= sa;
+      db *= sb;
+    }
     float oa = da, ob = db;
     if (r.kind < 2) {
       float s, c;
@@ -307,84 +388,86 @@ __global__ __launch_bounds__(kGemvThreads) void qkv_rope_kernel(QkvArgs a) {
       kv_store_pair<DT>(cache, off, half, oa, ob, a.kv_fmt);
     }
   };
-  run_pairs<DT, true, U, PFC>(map, epi, xs, a.K, npairs, p0, gridDim.x * kGemvWaves, pre);
+  run_pairs<F, DT, true, U, PFC>(map, epi, xs, a.K, npairs, p0, gridDim.x * kGemvWaves, pre);
 }
 
 // ---------------------------------------------------------------------------
 // RMSNorm + gate/up + SiLU*mul
 // ---------------------------------------------------------------------------
-template <int DT, int U, int PFC, int NX>
+template <class F, int DT, int U, int PFC, int NX>
 __global__ __launch_bounds__(kGemvThreads) void swiglu_kernel(
     const float* __restrict__ resid, const uint16_t* __restrict__ norm_w, float eps,
-    const uint16_t* __restrict__ wg, const uint16_t* __restrict__ wu, int K, int I,
+    const typename F::Mat wg, const typename F::Mat wu, int K, int I,
     uint16_t* __restrict__ act) {
   extern __shared__ float xs[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int j0 = blockIdx.x * kGemvWaves + wave;
-  auto map = [&](int j, const uint16_t*& wa, const uint16_t*& wb) {
-    wa = wg + (size_t)j * K;
-    wb = wu + (size_t)j * K;
-  };
-  Regs<PFC> pre;
-  NormPre<DT, NX> xp;
+  auto map = [&](int j) { return F::rows(wg, (size_t)j, wu, (size_t)j, K); };
+  Regs<F, PFC> pre;
+  NormPre<F, DT, NX> xp;
   const int jp = j0 < I ? j0 : I - 1;
-  const uint16_t *wa0 = wg + (size_t)jp * K, *wb0 = wu + (size_t)jp * K;
+  const typename F::Rows r0 = map(jp);
   if constexpr (NX > 0) xp.load(resid, norm_w, K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
   // NX: unconditional (an idle wave re-reads the last row), so the vmcnt is exact
-  if (NX > 0 || (PFC > 0 && j0 < I)) prefetch_rows<PFC>(wa0, wb0, pre);
+  if (NX > 0 || (PFC > 0 && j0 < I)) prefetch_rows<F, PFC>(r0, pre);
+  const float s0g = row_scale<F>(wg, jp), s0u = row_scale<F>(wu, jp);  // requested now
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (NX > 0) xp.finish(eps, K, xs);
-  else stage_rmsnorm<DT>(resid, norm_w, eps, K, xs);
+  else stage_rmsnorm<F, DT>(resid, norm_w, eps, K, xs);
   auto epi = [&](int j, float g, float u) {
-    if (lane == 0) act[j] = from_f32<DT>(silu(g) * u);
+    if (lane != 0) return;
+    g = descale<F>(g, j == j0, s0g, wg, j);
+    u = descale<F>(u, j == j0, s0u, wu, j);
+    act[j] = from_f32<DT>(silu(g) * u);
   };
-  run_pairs<DT, true, U, PFC>(map, epi, xs, K, I, j0, gridDim.x * kGemvWaves, pre);
+  run_pairs<F, DT, true, U, PFC>(map, epi, xs, K, I, j0, gridDim.x * kGemvWaves, pre);
 }
 
 // ---------------------------------------------------------------------------
 // out (+)= W x   with 16-bit x: o_proj / down_proj (accumulate into the f32
 // residual stream) — or plain f32 output.
 // ---------------------------------------------------------------------------
-template <int DT, int U, int PFC, int NX, bool ACCUM>
+template <class F, int DT, int U, int PFC, int NX, bool ACCUM>
 __global__ __launch_bounds__(kGemvThreads) void gemv_x16_kernel(
-    const uint16_t* __restrict__ x, const uint16_t* __restrict__ w, int K, int N,
+    const uint16_t* __restrict__ x, const typename F::Mat w, int K, int N,
     float* __restrict__ out) {
   extern __shared__ float smem[];
   uint16_t* xs = reinterpret_cast<uint16_t*>(smem);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int npairs = (N + 1) >> 1;
   const int p0 = blockIdx.x * kGemvWaves + wave;
-  auto map = [&](int p, const uint16_t*& wa, const uint16_t*& wb) {
-    wa = w + (size_t)(2 * p) * K;
-    wb = w + (size_t)min(2 * p + 1, N - 1) * K;
-  };
-  Regs<PFC> pre;
-  Plain16Pre<NX> xp;
-  const uint16_t *wa0, *wb0;
-  map(p0 < npairs ? p0 : npairs - 1, wa0, wb0);
+  auto map = [&](int p) { return F::rows(w, (size_t)(2 * p), w, (size_t)min(2 * p + 1, N - 1), K); };
+  Regs<F, PFC> pre;
+  Plain16Pre<F, NX> xp;
+  const int pc = p0 < npairs ? p0 : npairs - 1;
+  const typename F::Rows r0 = map(pc);
   if constexpr (NX > 0) xp.load(x, K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
-  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<PFC>(wa0, wb0, pre);  // NX: exact vmcnt
-  // ACCUM: the residual words of the wave's first pair, requested now (read in
-  // the epilogue they were one more memory round trip at the end of every wave;
-  // no other wave of this launch writes them)
+  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
+  // the epilogue operands of the wave's first pair, requested now: the row scales and
+  // (ACCUM) the residual words (read in the epilogue they were one more memory round trip
+  // at the end of every wave; no other wave of this launch writes them)
+  const float s0a = row_scale<F>(w, 2 * pc), s0b = row_scale<F>(w, min(2 * pc + 1, N - 1));
   float r0a = 0.f, r0b = 0.f;
   if constexpr (ACCUM) {
-    const int pc = p0 < npairs ? p0 : npairs - 1;
     r0a = out[2 * pc];
     r0b = out[min(2 * pc + 1, N - 1)];
   }
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (NX > 0) xp.finish(K, xs);
-  else stage_plain16(x, K, xs);
+  else stage_plain16<F>(x, K, xs);
   auto epi = [&](int p, float da, float db) {
     if (lane != 0) return;
     const int ra = 2 * p, rb = 2 * p + 1;
+    da = descale<F>(da, p == p0, s0a, w, ra);
     if (ACCUM) out[ra] = da + (p == p0 ? r0a : out[ra]); else out[ra] = da;
-    if (rb < N) { if (ACCUM) out[rb] = db + (p == p0 ? r0b : out[rb]); else out[rb] = db; }
+    if (rb < N) {
+      db = descale<F>(db, p == p0, s0b, w, rb);
+      if (ACCUM) out[rb] = db + (p == p0 ? r0b : out[rb]); else out[rb] = db;
+    }
   };
-  run_pairs<DT, false, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
+  run_pairs<F, DT, false, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
 }
 
 // Greedy token selection fused into the lm_head (SEL): repeat penalty on the logits of
@@ -413,121 +496,6 @@ __device__ __forceinline__ unsigned int ordered_key(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// RMSNorm(f32 row) then f32 output: the lm_head (SEL: + greedy selection, see HeadSel).
-template <int DT, int U, int PFC, int NX, bool SEL>
-__global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_kernel(
-    const float* __restrict__ resid, const uint16_t* __restrict__ norm_w, float eps,
-    const uint16_t* __restrict__ w, int K, int N, float* __restrict__ out, HeadSel hs) {
-  extern __shared__ float xs[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int npairs = (N + 1) >> 1;
-  const int p0 = blockIdx.x * kGemvWaves + wave;
-  auto map = [&](int p, const uint16_t*& wa, const uint16_t*& wb) {
-    wa = w + (size_t)(2 * p) * K;
-    wb = w + (size_t)min(2 * p + 1, N - 1) * K;
-  };
-  // SEL: the history length is requested ahead of the x prologue (one load in front of
-  // it), the window itself after it (queued behind the first weight rows; first needed
-  // by the first pair's epilogue)
-  int hlen = 0;
-  if constexpr (SEL) hlen = hs.penalty != 1.f ? *hs.hist_len : 0;
-  Regs<PFC> pre;
-  NormPre<DT, NX> xp;
-  const uint16_t *wa0, *wb0;
-  map(p0 < npairs ? p0 : npairs - 1, wa0, wb0);
-  if constexpr (NX > 0) xp.load(resid, norm_w, K);
-  __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
-  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<PFC>(wa0, wb0, pre);  // NX: exact vmcnt
-  __builtin_amdgcn_sched_barrier(0);
-  if constexpr (NX > 0) xp.finish(eps, K, xs);
-  else stage_rmsnorm<DT>(resid, norm_w, eps, K, xs);
-  int win[4] = {-1, -1, -1, -1};
-  if constexpr (SEL) {
-    const int n = min(hs.last_n, hlen), start = hlen - n;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (j * 64 + lane < n) win[j] = hs.hist[start + j * 64 + lane];
-  }
-  unsigned long long best = 0ull;
-  auto epi = [&](int p, float da, float db) {
-    const int ra = 2 * p, rb = 2 * p + 1;
-    if constexpr (SEL) {
-      // penalty: the row is one of the window's tokens (each token once, like the
-      // unique-token loop of repeat_penalty_kernel)
-      if (hs.penalty != 1.f) {
-        const bool ia = win[0] == ra || win[1] == ra || win[2] == ra || win[3] == ra;
-        const bool ib = win[0] == rb || win[1] == rb || win[2] == rb || win[3] == rb;
-        if (__builtin_amdgcn_ballot_w64(ia) != 0ull) da = da >= 0.f ? da / hs.penalty : da * hs.penalty;
-        if (__builtin_amdgcn_ballot_w64(ib) != 0ull) db = db >= 0.f ? db / hs.penalty : db * hs.penalty;
-      }
-      const unsigned long long ka =
-          ((unsigned long long)ordered_key(da) << 32) | (0xffffffffu - (unsigned int)ra);
-      best = ka > best ? ka : best;
-      if (rb < N) {
-        const unsigned long long kb =
-            ((unsigned long long)ordered_key(db) << 32) | (0xffffffffu - (unsigned int)rb);
-        best = kb > best ? kb : best;
-      }
-    }
-    if (lane != 0) return;
-    out[ra] = da;
-    if (rb < N) out[rb] = db;
-  };
-  run_pairs<DT, true, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
-  if constexpr (SEL) {
-    // block max -> one returning 8-byte device atomic on the slot, drained before the
-    // ticket (atomics on both sides: the last workgroup reads the slot atomically)
-    __shared__ unsigned long long red[kGemvWaves];
-    __shared__ int is_last;
-    if (lane == 0) red[wave] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      unsigned long long b = red[0];
-#pragma unroll
-      for (int i = 1; i < kGemvWaves; ++i) b = red[i] > b ? red[i] : b;
-      const unsigned long long old =
-          __hip_atomic_fetch_max(hs.slot, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::"v"((unsigned int)old) : "memory");
-      const unsigned int t =
-          __hip_atomic_fetch_add(hs.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      is_last = t == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (is_last) {  // block-uniform
-      __shared__ int sel_tok;
-      if (threadIdx.x == 0) {
-        const unsigned long long key =
-            __hip_atomic_fetch_max(hs.slot, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int t = (int)(0xffffffffu - (unsigned int)(key & 0xffffffffull));
-        *hs.tok = t;
-        const int len = *hs.hist_len_w;
-        if (len < hs.max_hist) { hs.hist_w[len] = t; *hs.hist_len_w = len + 1; }
-        *hs.pos += 1;
-        // re-arm for the next launch (the kernel boundary orders these for it)
-        __hip_atomic_store(hs.slot, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(hs.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        sel_tok = t;
-      }
-      if (hs.embed != nullptr) {
-        // the next step's input row (what embed_kernel would launch for): every other
-        // workgroup has finished reading resid (their tickets preceded this one)
-        __syncthreads();
-        const uint16_t* row = hs.embed + (size_t)sel_tok * hs.H;
-        for (int i = threadIdx.x * 8; i < hs.H; i += kGemvThreads * 8) {
-          float f[8];
-          unpack8<DT>(*reinterpret_cast<const uint4*>(row + i), f);
-          *reinterpret_cast<float4*>(hs.emb_out + i) = make_float4(f[0], f[1], f[2], f[3]);
-          *reinterpret_cast<float4*>(hs.emb_out + i + 4) = make_float4(f[4], f[5], f[6], f[7]);
-        }
-      }
-    }
-  }
-}
-
-// The SEL pieces of gemv_norm_f32_kernel as helpers, shared by its quantised twins
-// (gemv_norm_f32_w8_kernel, gemv_norm_f32_w4_kernel).  The 16-bit kernel keeps its own
-// inline copy: its code generation is the measured baseline of the default path.
-
 // the lane's share of the penalty window (4 tokens per lane, -1 = none)
 __device__ __forceinline__ void head_sel_window(const HeadSel& hs, int hlen, int lane, int* win) {
   const int n = min(hs.last_n, hlen), start = hlen - n;
@@ -535,7 +503,9 @@ __device__ __forceinline__ void head_sel_window(const HeadSel& hs, int hlen, int
   for (int j = 0; j < 4; ++j) win[j] = j * 64 + lane < n ? hs.hist[start + j * 64 + lane] : -1;
 }
 
-// penalty on the pair's (wave-uniform) logits and the running best key of the wave
+// penalty on the pair's (wave-uniform) logits — the row is one of the window's tokens, each
+// token once, like the unique-token loop of repeat_penalty_kernel — and the running best key
+// of the wave
 __device__ __forceinline__ void head_sel_pair(const HeadSel& hs, const int* win, int ra, int rb,
                                               int N, float& da, float& db,
                                               unsigned long long& best) {
@@ -555,8 +525,10 @@ __device__ __forceinline__ void head_sel_pair(const HeadSel& hs, const int* win,
   }
 }
 
-// block max -> one returning 8-byte device atomic on the slot, drained before the ticket;
-// the last workgroup finalizes the step and gathers the next input row (16-bit table).
+// block max -> one returning 8-byte device atomic on the slot, drained before the ticket
+// (atomics on both sides: the last workgroup reads the slot atomically); the last workgroup
+// finalizes the step and gathers the next input row (16-bit table: what embed_kernel would
+// launch for).
 // Its words live in `lds`, the start of the kernel's dynamic LDS (the x row, dead after the
 // pair loop; >= 64 bytes), not in static __shared__ variables: those sit in front of the
 // dynamic region, and the 40 bytes they took left its base 8 bytes off a 16-byte boundary,
@@ -611,18 +583,51 @@ __device__ __forceinline__ void head_sel_tail(const HeadSel& hs, unsigned long l
   }
 }
 
-// Launch geometry per kernel kind (tunable at run time; defaults from the
-// rocprofv3-measured sweep in profiles/): U = chunks in flight per row,
-// PF = prefetch the first weight batch before the x prologue, MB = grid cap.
-struct GemvTune { int U, PF, MB; };
-// kX16 = 16-bit-input GEMVs with K > 8192 (down_proj), kX16S = K <= 8192 (o_proj)
-enum GemvKind { kQkv = 0, kSwiglu = 1, kX16 = 2, kNormF32 = 3, kX16S = 4, kNumKinds = 5 };
-// measured in the decode graph (8B, tok/s): profiles/r2_gemv_split_prologue_sweep*.jsonl —
-// prefetching the first weight rows behind the split x prologue is +10% (323 -> 357); the
-// round-3 re-sweep (profiles/r3_decode_gemv_tuning_ingraph.jsonl) moved QKV to U 2 / PF 4
-// (+0.3 %, every round) and left the rest
-// the run-time tuning table (defined in gemv.hip, set by cake_gemv_set_tuning)
-extern GemvTune g_tune[kNumKinds];
+// RMSNorm(f32 row) then f32 output: the lm_head (SEL: + greedy selection, see HeadSel; the
+// next input row comes from the 16-bit embedding table whatever the head's format).
+template <class F, int DT, int U, int PFC, int NX, bool SEL>
+__global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_kernel(
+    const float* __restrict__ resid, const uint16_t* __restrict__ norm_w, float eps,
+    const typename F::Mat w, int K, int N, float* __restrict__ out, HeadSel hs) {
+  extern __shared__ float xs[];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int npairs = (N + 1) >> 1;
+  const int p0 = blockIdx.x * kGemvWaves + wave;
+  auto map = [&](int p) { return F::rows(w, (size_t)(2 * p), w, (size_t)min(2 * p + 1, N - 1), K); };
+  // SEL: the history length is requested ahead of the x prologue (one load in front of
+  // it), the window itself after it (queued behind the first weight rows; first needed
+  // by the first pair's epilogue)
+  int hlen = 0;
+  if constexpr (SEL) hlen = hs.penalty != 1.f ? *hs.hist_len : 0;
+  Regs<F, PFC> pre;
+  NormPre<F, DT, NX> xp;
+  const int pc = p0 < npairs ? p0 : npairs - 1;
+  const typename F::Rows r0 = map(pc);
+  if constexpr (NX > 0) xp.load(resid, norm_w, K);
+  __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
+  if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
+  // the first pair's row scales, requested now (one address per wave: every lane holds
+  // the value, which the SEL ballot and key need wave-wide)
+  const float s0a = row_scale<F>(w, 2 * pc), s0b = row_scale<F>(w, min(2 * pc + 1, N - 1));
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (NX > 0) xp.finish(eps, K, xs);
+  else stage_rmsnorm<F, DT>(resid, norm_w, eps, K, xs);
+  int win[4] = {-1, -1, -1, -1};
+  if constexpr (SEL) head_sel_window(hs, hlen, lane, win);
+  unsigned long long best = 0ull;
+  auto epi = [&](int p, float da, float db) {
+    const int ra = 2 * p, rb = 2 * p + 1;
+    // the row scales first: everything below sees the logits
+    da = descale<F>(da, p == p0, s0a, w, ra);
+    db = descale<F>(db, p == p0, s0b, w, min(rb, N - 1));
+    if constexpr (SEL) head_sel_pair(hs, win, ra, rb, N, da, db, best);
+    if (lane != 0) return;
+    out[ra] = da;
+    if (rb < N) out[rb] = db;
+  };
+  run_pairs<F, DT, true, U, PFC>(map, epi, xs, K, npairs, p0, gridDim.x * kGemvWaves, pre);
+  if constexpr (SEL) head_sel_tail<DT>(hs, best, xs);
+}
 
 static inline int grid_for(int npairs, int max_blocks) {
   int g = (npairs + kGemvWaves - 1) / kGemvWaves;
@@ -633,6 +638,11 @@ static inline int grid_for(int npairs, int max_blocks) {
 
 using namespace cake;
 
+// ---------------------------------------------------------------------------
+// Launchers: one per kernel kind, shared by the formats.  The cake_* entry points
+// (gemv*.hip) cast their pointers into F::Mat handles and call these.
+// ---------------------------------------------------------------------------
+
 #define DISPATCH_DT(dt, ...)                       \
   do {                                             \
     if ((dt) == kBF16) { constexpr int DT = kBF16; __VA_ARGS__; } \
@@ -640,12 +650,20 @@ using namespace cake;
     else return (int)hipErrorInvalidValue;         \
   } while (0)
 
-// Expand BODY for the run-time (U, PFC) choice; PFC falls back to 0 when a
-// row is shorter than PFC*64 chunks (small test shapes).
-#define CAKE_TUNE_U(PFCV, ...)                                                       \
-  if (t.U == 2) { constexpr int U = 2; constexpr int PF = PFCV; __VA_ARGS__; }       \
-  else if (t.U == 8) { constexpr int U = 8; constexpr int PF = PFCV; __VA_ARGS__; }  \
-  else { constexpr int U = 4; constexpr int PF = PFCV; __VA_ARGS__; }
+// Expand BODY for the run-time (U, PF) choice among those format F instantiates: t.U is one
+// of F::kU (gemv_set_tuning refuses any other), the prefetch depth is what F::prefetch makes
+// of t.PF for a row of K values (one of F::kPF, or 0).
+#define CAKE_TUNE_U(F, PFCV, ...)                                                              \
+  if (t.U == F::kU[0]) { constexpr int U = F::kU[0]; constexpr int PF = PFCV; __VA_ARGS__; }      \
+  else if (t.U == F::kU[1]) { constexpr int U = F::kU[1]; constexpr int PF = PFCV; __VA_ARGS__; } \
+  else { constexpr int U = F::kU[2]; constexpr int PF = PFCV; __VA_ARGS__; }
+#define DISPATCH_TUNE(F, t, K, ...)                                                  \
+  do {                                                                               \
+    const int pfc_ = F::prefetch((t).PF, K);                                         \
+    if (pfc_ == F::kPF[0]) { CAKE_TUNE_U(F, F::kPF[0], __VA_ARGS__) }                \
+    else if (pfc_ == F::kPF[1]) { CAKE_TUNE_U(F, F::kPF[1], __VA_ARGS__) }           \
+    else { CAKE_TUNE_U(F, 0, __VA_ARGS__) }                                          \
+  } while (0)
 // NX: split x prologue (only with a weight prefetch): RMSNorm rows K <= 1024 NX,
 // 16-bit rows K <= 2048 NX (guarded tails: the TP shards' K); larger K use the
 // plain prologue (NX = 0).
@@ -664,11 +682,115 @@ using namespace cake;
     else if ((K) <= 28672) { constexpr int NX = 14; __VA_ARGS__; }                   \
     else { constexpr int NX = 0; __VA_ARGS__; }                                      \
   } else { constexpr int NX = 0; __VA_ARGS__; }
-#define DISPATCH_TUNE(t, K, ...)                                                     \
-  do {                                                                               \
-    const int pfc_ = ((K) / 8 >= 64 * (t).PF) ? (t).PF : 0;                          \
-    if (pfc_ == 8) { CAKE_TUNE_U(8, __VA_ARGS__) }                                   \
-    else if (pfc_ == 4) { CAKE_TUNE_U(4, __VA_ARGS__) }                              \
-    else { CAKE_TUNE_U(0, __VA_ARGS__) }                                             \
-  } while (0)
 
+// K must be whole chunks; kStrict: at least one, and n (the output rows) at least 1
+template <class F> static inline bool bad_shape(int K, int n) {
+  return K % (1 << F::kLog2) != 0 || (F::kStrict && (K < (1 << F::kLog2) || n < 1));
+}
+template <class F> static inline size_t x32_lds_bytes(int K) {
+  return (size_t)((K + F::kPad32 - 1) / F::kPad32 * F::kPad32) * sizeof(float);
+}
+template <class F> static inline size_t x16_lds_bytes(int K) {
+  return (size_t)((K + F::kPad16 - 1) / F::kPad16 * F::kPad16) * sizeof(uint16_t);
+}
+
+template <class F> static int gemv_set_tuning(int kind, int U, int prefetch, int max_blocks) {
+  if (kind < 0 || kind >= F::kKinds || (U != F::kU[0] && U != F::kU[1] && U != F::kU[2]) ||
+      max_blocks < 1 || (prefetch != 0 && prefetch != F::kPF[0] && prefetch != F::kPF[1]))
+    return (int)hipErrorInvalidValue;
+  g_tune[F::kFmt][kind] = GemvTune{U, prefetch, max_blocks};
+  return 0;
+}
+
+template <class F> static int gemv_get_tuning(int kind, int* out3) {
+  if (kind < 0 || kind >= F::kKinds || !out3) return (int)hipErrorInvalidValue;
+  const GemvTune t = g_tune[F::kFmt][kind];
+  out3[0] = t.U;
+  out3[1] = t.PF;
+  out3[2] = t.MB;
+  return 0;
+}
+
+// kv_fmt (common.h KvFmt): 0 = 16-bit cache rows, 1 = kcache / vcache hold one e4m3fn code
+// per element (quant_kv_fp8 of the f32 roped K / f32 V), 2 = those codes' values as 16 bits
+template <class F> static int launch_qkv(int dt, const QkvArgs<F>& a, hipStream_t st) {
+  if (bad_shape<F>(a.K, a.nh < a.nkv ? a.nh : a.nkv) || a.hd % 2 || a.kv_fmt < 0 || a.kv_fmt > 2)
+    return (int)hipErrorInvalidValue;
+  const int K = a.K, npairs = (a.nh + 2 * a.nkv) * (a.hd / 2);
+  const size_t lds = x32_lds_bytes<F>(K);
+  const GemvTune t = g_tune[F::kFmt][kQkv];
+  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((qkv_rope_kernel<F, DT, U, PF, NX>),
+                                                         dim3(grid_for(npairs, t.MB)),
+                                                         dim3(kGemvThreads), lds, st, a))));
+  return (int)hipGetLastError();
+}
+
+template <class F>
+static int launch_swiglu(int dt, const float* resid, const void* norm_w, float eps,
+                         typename F::Mat wg, typename F::Mat wu, int K, int I, void* act,
+                         hipStream_t st) {
+  if (bad_shape<F>(K, I)) return (int)hipErrorInvalidValue;
+  const size_t lds = x32_lds_bytes<F>(K);
+  const GemvTune t = g_tune[F::kFmt][kSwiglu];
+  // at least one block per 28 rows (7 row pairs per wave): 70B's I = 28672 runs 1024
+  // blocks (+0.7 %, profiles/r2_decode_gemv_tuning_70b.jsonl), 8B's 14336 the tuned cap
+  const int mb = t.MB > (I + 27) / 28 ? t.MB : (I + 27) / 28;
+  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((swiglu_kernel<F, DT, U, PF, NX>),
+                                                         dim3(grid_for(I, mb)), dim3(kGemvThreads),
+                                                         lds, st, resid, (const uint16_t*)norm_w, eps,
+                                                         wg, wu, K, I, (uint16_t*)act))));
+  return (int)hipGetLastError();
+}
+
+template <class F>
+static int launch_x16(int dt, const void* x, typename F::Mat w, int K, int N, float* out,
+                      int accumulate, hipStream_t st) {
+  if (bad_shape<F>(K, N)) return (int)hipErrorInvalidValue;
+  const size_t lds = x16_lds_bytes<F>(K);
+  const GemvTune t = g_tune[F::kFmt][F::kKinds > kX16S && K <= 8192 ? kX16S : kX16];
+  const int g = grid_for((N + 1) / 2, t.MB);
+  if (accumulate) {
+    DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, true>),
+                                                          dim3(g), dim3(kGemvThreads), lds, st,
+                                                          (const uint16_t*)x, w, K, N, out))));
+  } else {
+    DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, false>),
+                                                          dim3(g), dim3(kGemvThreads), lds, st,
+                                                          (const uint16_t*)x, w, K, N, out))));
+  }
+  return (int)hipGetLastError();
+}
+
+template <class F, bool SEL>
+static int launch_norm_f32(int dt, const float* resid, const void* norm_w, float eps,
+                           typename F::Mat w, int K, int N, float* out, const HeadSel& hs,
+                           hipStream_t st) {
+  if (bad_shape<F>(K, N)) return (int)hipErrorInvalidValue;
+  // SEL: at least the 64 bytes head_sel_tail keeps its words in (a 16-bit K of 8)
+  const size_t lds = SEL && x32_lds_bytes<F>(K) < 64 ? 64 : x32_lds_bytes<F>(K);
+  const GemvTune t = g_tune[F::kFmt][kNormF32];
+  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((gemv_norm_f32_kernel<F, DT, U, PF, NX, SEL>),
+                                                         dim3(grid_for((N + 1) / 2, t.MB)),
+                                                         dim3(kGemvThreads), lds, st, resid,
+                                                         (const uint16_t*)norm_w, eps, w, K, N,
+                                                         out, hs))));
+  return (int)hipGetLastError();
+}
+
+// lm_head + repeat penalty + argmax + step finalizer in one launch (greedy decode);
+// with `embed`, also the next step's input emb_out[K] = embed[tok] (f32).  slot (u64)
+// and ticket (u32) must be zero before the first launch; the kernel re-arms them.
+// last_n <= 256.
+template <class F>
+static int launch_head_select(int dt, const float* resid, const void* norm_w, float eps,
+                              typename F::Mat w, int K, int N, float* out, int* hist,
+                              int* hist_len, int last_n, float penalty, unsigned long long* slot,
+                              unsigned int* ticket, int* tok, int* pos, int max_hist,
+                              const void* embed, float* emb_out, hipStream_t st) {
+  if (last_n < 0 || last_n > 256 || !(penalty > 0.f) || slot == nullptr || ticket == nullptr ||
+      (embed != nullptr && emb_out == nullptr))
+    return (int)hipErrorInvalidValue;
+  const HeadSel hs{hist, hist_len, last_n, penalty, slot, ticket, tok, hist, hist_len, pos,
+                   max_hist, (const uint16_t*)embed, emb_out, K};
+  return launch_norm_f32<F, true>(dt, resid, norm_w, eps, w, K, N, out, hs, st);
+}

@@ -1,4 +1,4 @@
-// MXFP4 decode helpers shared by quant_mxfp4.hip and the _w4 GEMVs (gemv_w4_kernel.h).
+// MXFP4 decode helpers shared by quant_mxfp4.hip and the MXFP4 GEMV format (gemv_w4_kernel.h).
 #pragma once
 #include "common.h"
 

@@ -183,15 +183,16 @@ def _bytes(n, k, fp8):
 
 def _classify(name):
     """(row label, twin key, bytes) of a decode GEMV kernel name, or None."""
-    m = re.search(r"(qkv_rope|swiglu|gemv_x16)(_w8)?_kernel<([^>]*)>", name)
+    # the weight format is the kernels' first template argument (cake::W16 / W8 / W4)
+    m = re.search(r"(qkv_rope|swiglu|gemv_x16)_kernel<(?:cake::)?W(16|8), ([^>]*)>", name)
     if not m:
         return None
-    kind, w8, targs = m.group(1), bool(m.group(2)), [t.strip() for t in m.group(3).split(",")]
+    kind, w8, targs = m.group(1), m.group(2) == "8", [t.strip() for t in m.group(3).split(",")]
     if kind == "qkv_rope":
         return f"qkv_rope{'_w8' if w8 else ''}", "qkv_rope", _bytes(NQKV, H, w8)
     if kind == "swiglu":
         return f"swiglu{'_w8' if w8 else ''}", "swiglu", _bytes(2 * I, H, w8)
-    # template <DT, U, PFC, NX, ACCUM>: NX tells o_proj (K = 4096 -> 2) from down_proj (K = 14336 -> 7)
+    # template <F, DT, U, PFC, NX, ACCUM>, F stripped: NX tells o_proj (K = 4096 -> 2) from down_proj (K = 14336 -> 7)
     nx = int(re.sub(r"\D", "", targs[3]) or 0)
     if nx == 7:
         return f"down_proj{'_w8' if w8 else ''}", "down_proj", _bytes(H, I, w8)

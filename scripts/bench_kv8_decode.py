@@ -125,11 +125,13 @@ def run(a):
 
 def _classify(name):
     """Row label of a decode attention / QKV launch, or None."""
-    m = re.search(r"(attn2_decode_kv8|attn2_decode|qkv_rope_w4|qkv_rope_w8|qkv_rope|"
+    m = re.search(r"(attn2_decode_kv8|attn2_decode|qkv_rope|"
                   r"dequant_kv_fp8|rope_kv_vec_q8|rope_kv_vec)_kernel<([^>]*)>", name)
     if not m:
         return None
     targs = [t.strip() for t in m.group(2).split(",")]
+    if m.group(1) == "qkv_rope":  # <F, ...>: the weight format cake::W16 / W8 / W4
+        return "qkv_rope" + {"W16": "", "W8": "_w8", "W4": "_w4"}[targs[0].split("::")[-1]]
     if m.group(1).startswith("attn2"):  # <DT, HD, NREP, PFD>
         return f"{m.group(1)} (prefetch {re.sub(r'[^0-9]', '', targs[3])})"
     return m.group(1)

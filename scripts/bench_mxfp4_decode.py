@@ -181,15 +181,20 @@ def _bytes(n, k, sfx):
 
 def _classify(name):
     """(row label, twin key, bytes) of a decode GEMV kernel name, or None."""
-    m = re.search(r"(qkv_rope|swiglu|gemv_x16)(_w8|_w4)?_kernel<([^>]*)>", name)
+    # the weight format is the kernels' first template argument (cake::W16 / W8 / W4)
+    m = re.search(r"(qkv_rope|swiglu|gemv_x16)_kernel<(?:cake::)?W(16|8|4), ([^>]*)>", name)
+    if not m:
+        # the MXFP4 gemv_x16 is a kernel of its own (gemv_w4_x16.hip): <DT, U, PFC, NX, ACCUM>
+        m = re.search(r"(gemv_x16)_w(4)_kernel<([^>]*)>", name)
     if not m:
         return None
-    kind, sfx, targs = m.group(1), m.group(2) or "", [t.strip() for t in m.group(3).split(",")]
+    kind, targs = m.group(1), [t.strip() for t in m.group(3).split(",")]
+    sfx = {"16": "", "8": "_w8", "4": "_w4"}[m.group(2)]
     if kind == "qkv_rope":
         return "qkv_rope" + sfx, "qkv_rope", _bytes(NQKV, H, sfx)
     if kind == "swiglu":
         return "swiglu" + sfx, "swiglu", _bytes(2 * I, H, sfx)
-    # template <DT, U, PFC, NX, ACCUM>: NX tells o_proj (K = 4096 -> 2) from down_proj (14336 -> 7)
+    # template <F, DT, U, PFC, NX, ACCUM>, F stripped: NX tells o_proj (K = 4096 -> 2) from down_proj (14336 -> 7)
     nx = int(re.sub(r"\D", "", targs[3]) or 0)
     if nx == 7:
         return "down_proj" + sfx, "down_proj", _bytes(H, I, sfx)

@@ -201,11 +201,13 @@ def table(path):
     rows = {}
     with open(path, newline="") as f:
         for r in csv.DictReader(f):
-            m = re.search(r"gemv_norm_f32(_w8|_w4)?_kernel<([^>]*)>", r["Name"])
+            # the weight format is the kernel's first template argument (cake::W16 / W8 / W4)
+            m = re.search(r"gemv_norm_f32_kernel<(?:cake::)?W(16|8|4), ([^>]*)>", r["Name"])
             if not m:
                 continue
             sel = m.group(2).split(",")[-1].strip() in ("true", "1")
-            e = rows.setdefault((m.group(1) or "", sel), {"calls": 0, "ns": 0.0})
+            sfx = {"16": "", "8": "_w8", "4": "_w4"}[m.group(1)]
+            e = rows.setdefault((sfx, sel), {"calls": 0, "ns": 0.0})
             e["calls"] += int(r["Calls"])
             e["ns"] += float(r["TotalDurationNs"])
 

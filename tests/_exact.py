@@ -352,6 +352,47 @@ def gemv_case(K: int, N: int, dtype, device="cpu") -> dict:
                 yacc=exact_linear(x[None], w, None, out0[None])[0])
 
 
+# --- decode GEMV over quantised weights ----------------------------------------
+
+GEMV_FMT_KS = [32, 2048, 4096, 14336]
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the value of an e2m1 code's low 3 bits
+
+
+def gemv_fmt_case(fmt: str, K: int, N: int, dtype, device="cpu") -> dict:
+    """Exact operands of the fp8 (`w8`) / MXFP4 (`w4`) decode GEMV: x integers, `quant` the
+    kernel's weight operands, y / yacc from exact_linear on their dequantised values.
+
+    w8: codes are the integers [-8, 8] as e4m3fn bytes, row scales 2^-2 .. 2^2: in units of
+    2^-2 a weight is at most 8 * 16, so K 14336 reaches 14336 * 8 * 128 + 4000 < 2^24.
+    w4: every e2m1 code (both zeros included), e8m0 bytes 125 .. 129 per 32-block: in units
+    of 2^-3 a weight is at most 6 * 4 * 8 = 192; |x| <= 8 keeps K <= 4096 below 2^24, and at
+    K 14336 x is drawn from [-6, 6] (14336 * 6 * 192 + 8000 < 2^24 <= 14336 * 7 * 192)."""
+    seed = 3 * (K + N) + (1 if fmt == "w8" else 2)
+    g = torch.Generator().manual_seed(seed)
+    if fmt == "w8":
+        x = int_operands((K,), -8, 8, dtype, seed)
+        codes = int_operands((N, K), -8, 8, torch.float32, seed + 1).to(torch.float8_e4m3fn)
+        scale = torch.ldexp(torch.ones(N), torch.randint(-2, 3, (N,), generator=g))
+        w = codes.float() * scale[:, None]
+        quant, w_unit = (codes.view(torch.uint8), scale), 2.0 ** -2
+    elif fmt == "w4":
+        w_unit = 2.0 ** -3
+        xmax = min(8, (2 ** 24 - 1 - int(1000 / w_unit)) // (K * 192))
+        x = int_operands((K,), -xmax, xmax, dtype, seed)
+        nib = torch.randint(0, 16, (N, K), generator=g)
+        e8 = torch.randint(125, 130, (N, K // 32), generator=g)
+        lut = torch.tensor(E2M1 + tuple(-v for v in E2M1))
+        w = torch.ldexp(lut[nib].reshape(N, -1, 32), (e8 - 127)[:, :, None]).reshape(N, K)
+        quant = ((nib[:, 0::2] | (nib[:, 1::2] << 4)).to(torch.uint8), e8.to(torch.uint8))
+    else:
+        raise ValueError(fmt)
+    out0 = int_operands((N,), -1000, 1000, torch.float32, seed + 2)
+    y = exact_linear(x[None], w, w_unit=w_unit)[0]
+    yacc = exact_linear(x[None], w, None, out0[None], w_unit=w_unit)[0]
+    return dict(x=x.to(device), quant=tuple(t.to(device) for t in quant), w=w,
+                out0=out0.to(device), y=y.to(device), yacc=yacc.to(device))
+
+
 # --- convolution -------------------------------------------------------------
 
 CONV_SHAPES = [(2, 9, 7, 128, 320, 3, 1, False), (1, 15, 17, 64, 64, 3, 2, False),

@@ -81,6 +81,16 @@ def test_gemv_cases(dt):
         for N in X.GEMV_NS:
             c = X.gemv_case(K, N, dt)
             assert c["y"].shape == (N,) and c["yacc"].dtype == torch.float32
+    from cake_amd.ops import reference as R
+    for K in X.GEMV_FMT_KS:
+        for N in X.GEMV_NS:
+            c = X.gemv_fmt_case("w8", K, N, dt)   # raises unless exact
+            assert torch.equal(R.dequant_rows_fp8(*c["quant"]), c["w"])
+            assert c["quant"][1].unique().numel() > (1 if N > 1 else 0)
+            c = X.gemv_fmt_case("w4", K, N, dt)
+            assert torch.equal(R.dequant_rows_mxfp4(*c["quant"]), c["w"])
+            assert (c["quant"][1].min(), c["quant"][1].max()) == (125, 129) or N * K // 32 < 64
+            assert float(c["x"].abs().max()) == (8 if K <= 4096 else 6)
 
 
 @pytest.mark.parametrize("dt", DTYPES)

@@ -195,3 +195,49 @@ def test_exact_gemv(cuda, gemv_tuning, dt, max_blocks, K):
         out = torch.full((N,), float("nan"), device=cuda)
         K_.gemv(c["x"], c["w"], out, accumulate=False)
         _same(out, c["y"], f"plain, N {N}")
+
+
+@pytest.fixture
+def quant_gemv_tuning():
+    from cake_amd.ops import hip as K_
+    prev8 = {k: K_.get_gemv_w8_tuning(k) for k in K_.GEMV_W8_KINDS}
+    prev4 = {k: K_.get_gemv_w4_tuning(k) for k in K_.GEMV_W4_KINDS}
+    yield K_
+    for k, (U, pf, mb) in prev8.items():
+        K_.set_gemv_w8_tuning(k, U=U, prefetch=pf, max_blocks=mb)
+    for k, (U, pf, mb) in prev4.items():
+        K_.set_gemv_w4_tuning(k, U=U, prefetch=pf, max_blocks=mb)
+
+
+@functools.lru_cache(maxsize=None)
+def _gemv_fmt_case(fmt, K, N, dt):
+    return X.gemv_fmt_case(fmt, K, N, dt, device="cuda")
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("max_blocks", [None, 3])
+@pytest.mark.parametrize("K", X.GEMV_FMT_KS)
+@pytest.mark.parametrize("fmt", ["w8", "w4"])
+def test_exact_gemv_formats(cuda, quant_gemv_tuning, fmt, dt, max_blocks, K):
+    """The fp8 and MXFP4 decode GEMVs (f32 out [+]= dequant(W) x), bit-equal to exact_linear
+    on the dequantised weights: integer x, fp8 codes that are integers with power-of-two
+    row scales, every e2m1 code with e8m0 bytes 125 .. 129 varying per 32-block
+    (_exact.gemv_fmt_case).  K 32 is one MXFP4 chunk (most of the wave idle in the tail
+    loop), 2048 / 4096 / 14336 the split x prologues (14336 the largest 16-bit one); idle
+    waves (N 1, 6), a ragged row count (257); default launch geometry and a grid capped at
+    3 blocks, where waves loop to pairs other than their first (the scales that are not
+    preloaded)."""
+    K_ = quant_gemv_tuning
+    get, put, run = {"w8": (K_.get_gemv_w8_tuning, K_.set_gemv_w8_tuning, K_.gemv_w8),
+                     "w4": (K_.get_gemv_w4_tuning, K_.set_gemv_w4_tuning, K_.gemv_w4)}[fmt]
+    if max_blocks is not None:
+        u, pf, _ = get("x16")
+        put("x16", U=u, prefetch=pf, max_blocks=max_blocks)
+    for N in X.GEMV_NS:
+        c = _gemv_fmt_case(fmt, K, N, dt)
+        out = c["out0"].clone()
+        run(c["x"], *c["quant"], out, accumulate=True)
+        _same(out, c["yacc"], f"{fmt} accumulate, N {N}")
+        out = torch.full((N,), float("nan"), device=cuda)
+        run(c["x"], *c["quant"], out, accumulate=False)
+        _same(out, c["y"], f"{fmt} plain, N {N}")

@@ -1,5 +1,6 @@
-"""Quantised lm_head kernels (gemv_w8_head.hip, gemv_w4_head.hip): the RMSNorm-prologue,
-f32-output GEMV over fp8 / MXFP4 rows and its fused greedy tail, against f32 torch math on
+"""Quantised lm_head kernels (gemv_norm_f32_kernel of gemv_kernel.h over the W8 / W4 weight
+formats; entry points gemv_w8_head.hip, gemv_w4_head.hip): the RMSNorm-prologue, f32-output
+GEMV over fp8 / MXFP4 rows and its fused greedy tail, against f32 torch math on
 the dequantised weights (ops/reference.py) and against the unfused launch chain."""
 import math
 
