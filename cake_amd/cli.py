@@ -106,6 +106,11 @@ def build_parser() -> argparse.ArgumentParser:
            "the activations quantised per token to e4m3 and multiplied with the resident fp8 "
            "codes (needs --weight-dtype fp8; not with --parallel tp; each worker's own flag "
            "governs its own layers); model = the weights' own prefill")
+    a("--score-file", default=None, metavar="PATH",
+      help="native Llama engine: score this UTF-8 text file instead of generating: "
+           "[bos] + its tokens in consecutive windows of --max-seq-len, teacher forced; one "
+           "JSON line {tokens, scored, windows, nll, ppl, top1} on stdout (any --weight-dtype "
+           "/ --head-dtype / --kv-dtype / --prefill-dtype; not with --parallel tp)")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -192,6 +197,28 @@ def prefill_dtype_refusal(ctx) -> str | None:
     return _quant_refusal(ctx, "--prefill-dtype", getattr(ctx, "prefill_dtype", "model"))
 
 
+def score_file_refusal(ctx) -> str | None:
+    """Why this context cannot run ``--score-file`` (None: it can, or the option is off), in
+    the wording of :func:`needs_native`: scoring is the native Llama engine's call, so every
+    Python engine path and every image model refuses."""
+    if not getattr(ctx, "score_file", None):
+        return None
+    a = ctx.args
+    native = ("--score-file is served by the native Llama engine only (a GPU, --dtype f16 or "
+              "bf16, hipGraph decode, CAKE_NATIVE not 0)")
+    if ctx.model_type != "text-model":
+        return native + ": it applies to the text model only"
+    if a.transport == "rccl" and getattr(a, "parallel", "pp") == "tp":
+        return ("--score-file is not supported with --parallel tp: a tensor-parallel engine "
+                "shards the vocabulary")
+    from .models.llama3.native_generator import native_eligible
+    if (not native_eligible(ctx) or a.transport != "tcp" or a.mode == "worker"
+            or getattr(a, "api", None)):
+        return native + ("; this run would take the Python path, which has no sequence "
+                         "scoring: refusing rather than generating")
+    return None
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -201,10 +228,16 @@ def _run(args) -> int:
     from .context import Context
     ctx = Context.from_args(args)
     why = (weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
-           or prefill_dtype_refusal(ctx))
+           or prefill_dtype_refusal(ctx) or score_file_refusal(ctx))
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2
+    if ctx.score_file:
+        import json
+
+        from .models.llama3.native_generator import score_file
+        print(json.dumps(score_file(ctx, ctx.score_file)), flush=True)
+        return 0
     if args.transport == "rccl":
         from .parallel.rccl_roles import run_rccl
         run_rccl(ctx)

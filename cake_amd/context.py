@@ -45,6 +45,7 @@ class Context:
     head_dtype: str = "model"    # --head-dtype: the lm_head's format, native engine only
     kv_dtype: str = "model"      # --kv-dtype: "fp8" = e4m3 KV cache, native engine only
     prefill_dtype: str = "model"  # --prefill-dtype: "fp8" = fp8 MFMA prefill, native engine only
+    score_file: str | None = None  # --score-file: score this text file instead of generating
 
     @classmethod
     def from_args(cls, args) -> "Context":
@@ -73,7 +74,8 @@ class Context:
                    weight_dtype=getattr(args, "weight_dtype", "model") or "model",
                    head_dtype=getattr(args, "head_dtype", "model") or "model",
                    kv_dtype=getattr(args, "kv_dtype", "model") or "model",
-                   prefill_dtype=getattr(args, "prefill_dtype", "model") or "model")
+                   prefill_dtype=getattr(args, "prefill_dtype", "model") or "model",
+                   score_file=getattr(args, "score_file", None) or None)
 
 
 def hbm_mib(device=None) -> dict:

@@ -98,6 +98,13 @@ int cake_gemv_x16_w8(int dt, const void* x, const void* w, const float* scale, i
 int cake_gemm_w8a8(int dt, int epi, int cfg, const void* a8, long long lda, const float* sa,
                    const void* w8, long long ldb, const float* sw, void* c, long long ldc,
                    float* r32, long long ldr, int M, int N, int K, hipStream_t st);
+// sequence scoring (score.hip): streaming log-sum-exp / target gather / argmax over one
+// vocabulary chunk of f32 logits, per-row state carried from chunk to chunk
+int cake_lse_rows(const float* logits, long long ld, int T, int Vc, int v0, int first,
+                  const int32_t* target, float* run_max, double* run_sum, float* tgt,
+                  unsigned long long* key, hipStream_t st);
+int cake_lse_finish(const float* run_max, const double* run_sum, const unsigned long long* key,
+                    int T, float* lse, int32_t* top, float* topv, hipStream_t st);
 // MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
 int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void* e8,
                           hipStream_t st);
@@ -612,6 +619,75 @@ class Llama {
     forced_run(prompt, T, forced, n, out);
   }
 
+  // Teacher-forced scoring of tokens[0, n): one prefill, then the head over every row in
+  // vocabulary chunks (a store32 GEMM into an f32 scratch [n, Vc], reduced in place by
+  // cake_lse_rows), so [n, V] logits never exist.  Row i: lse, the logit of tokens[i + 1]
+  // (NaN on the last row), the argmax id and its logit.  The engine is left as
+  // prefill_logits() leaves it.
+  void score(const int32_t* tokens, int n, int vchunk, float* lse, float* tgt, int32_t* top,
+             float* topv) {
+    hip_check(hipSetDevice(dev_), "hipSetDevice");
+    if (tp_ > 1)
+      throw Error("score() is not available on a tensor-parallel engine (the vocabulary is "
+                  "sharded)");
+    if (!head_) throw Error("score() runs on an engine that holds the head (pipeline rank 0)");
+    const int V = cfg_.V;
+    if (n < 2) throw Error("score() needs at least 2 tokens");
+    if (n > S_) throw Error("score(): " + std::to_string(n) + " tokens exceed max_seq " +
+                            std::to_string(S_));
+    for (int i = 0; i < n; ++i)
+      if (tokens[i] < 0 || tokens[i] >= V)
+        throw Error("score(): token id " + std::to_string(tokens[i]) + " at " +
+                    std::to_string(i) + " is outside [0, " + std::to_string(V) + ")");
+    int Vc = vchunk;
+    if (vchunk == 0) {  // the largest multiple of 256 with n Vc 4 bytes <= 64 MB
+      const long long fit = (64LL << 20) / (4LL * n) / 256 * 256;
+      Vc = (int)std::max<long long>(256, fit);
+    } else if (vchunk < 0 || vchunk % 256) {
+      throw Error("score(): vchunk is 0 or a positive multiple of 256, got " +
+                  std::to_string(vchunk));
+    }
+    Vc = std::min(Vc, V);
+    grow_score(n, Vc);
+    prefill_body(tokens, n);
+    const int H = cfg_.H;
+    std::vector<int32_t> target(tokens + 1, tokens + n);
+    target.push_back(-1);
+    hip_check(hipMemcpyAsync(sc_target_, target.data(), sizeof(int32_t) * n,
+                             hipMemcpyHostToDevice, st_), "targets H2D");
+    k_check(cake_rmsnorm(dt_, hidden_, norm_, (float)cfg_.eps, n, H, x16_, st_), "rmsnorm");
+    for (int v0 = 0; v0 < V; v0 += Vc) {
+      const int w = std::min(Vc, V - v0);
+      const void* rows;
+      if (hfmt_ == 1) {
+        k_check(cake_dequant_rows_fp8(dt_, head_q_ + (size_t)v0 * H, head_s_ + v0, w, H, sc_head_,
+                                      st_), "dequant_rows_fp8 lm_head");
+        rows = sc_head_;
+      } else if (hfmt_ == 2) {
+        k_check(cake_dequant_rows_mxfp4(dt_, head_q_ + (size_t)v0 * H / 2,
+                                        head_e_ + (size_t)v0 * H / 32, w, H, sc_head_, st_),
+                "dequant_rows_mxfp4 lm_head");
+        rows = sc_head_;
+      } else {
+        rows = (const uint16_t*)lm_head_ + (size_t)v0 * H;
+      }
+      gemm(kEpiStore32, x16_, H, rows, H, nullptr, 0, sc_logits_, Vc, n, w, H, "gemm score head");
+      k_check(cake_lse_rows(sc_logits_, Vc, n, w, v0, v0 == 0, sc_target_, sc_max_, sc_sum_,
+                            sc_tgt_, sc_key_, st_), "lse_rows");
+    }
+    k_check(cake_lse_finish(sc_max_, sc_sum_, sc_key_, n, sc_lse_, sc_top_, sc_topv_, st_),
+            "lse_finish");
+    hip_check(hipMemcpyAsync(lse, sc_lse_, sizeof(float) * n, hipMemcpyDeviceToHost, st_), "D2H");
+    hip_check(hipMemcpyAsync(tgt, sc_tgt_, sizeof(float) * n, hipMemcpyDeviceToHost, st_), "D2H");
+    hip_check(hipMemcpyAsync(top, sc_top_, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st_),
+              "D2H");
+    hip_check(hipMemcpyAsync(topv, sc_topv_, sizeof(float) * n, hipMemcpyDeviceToHost, st_),
+              "D2H");
+    hip_check(hipStreamSynchronize(st_), "sync");
+    if (world_ > 1) sync_workers();
+    check_attn_error("rank " + std::to_string(rank()));
+  }
+
   void generate(const int32_t* prompt, int T, int max_new, const CakeEngineSampling& smp,
                 const int32_t* eos, int n_eos, cake_engine_token_cb cb, void* ctx, int32_t* out,
                 int out_cap, CakeEngineStats* stats) {
@@ -983,6 +1059,15 @@ class Llama {
   int32_t* ptok_ = nullptr;
   uint8_t* a8_ = nullptr;       // prefill_fmt 1: [T, max(H, nq, I)] activation codes
   float* sa_ = nullptr;         // prefill_fmt 1: [T] activation scales
+  // scoring scratch (first score() call; grown like the prefill buffers): the f32 logit
+  // chunk [rows, Vc], the 16-bit copy of a quantised head's chunk [Vc, H], per-row state
+  int sc_T_ = 0, sc_Vc_ = 0;
+  float *sc_logits_ = nullptr, *sc_max_ = nullptr, *sc_tgt_ = nullptr, *sc_lse_ = nullptr,
+        *sc_topv_ = nullptr;
+  double* sc_sum_ = nullptr;
+  unsigned long long* sc_key_ = nullptr;
+  int32_t *sc_target_ = nullptr, *sc_top_ = nullptr;
+  uint16_t* sc_head_ = nullptr;
   float* ws_ = nullptr;
   size_t ws_n_ = 0;
   static constexpr size_t kLibWsBytes = 32u << 20;
@@ -1442,6 +1527,33 @@ class Llama {
       sa_ = dalloc<float>(T);
     }
     pre_T_ = T;
+  }
+
+  void grow_score(int T, int Vc) {
+    if (T > sc_T_) {
+      for (void* p : {(void*)sc_max_, (void*)sc_sum_, (void*)sc_tgt_, (void*)sc_key_,
+                      (void*)sc_lse_, (void*)sc_top_, (void*)sc_topv_, (void*)sc_target_})
+        dfree(p);
+      sc_max_ = dalloc<float>(T);
+      sc_sum_ = dalloc<double>(T);
+      sc_tgt_ = dalloc<float>(T);
+      sc_key_ = dalloc<unsigned long long>(T);
+      sc_lse_ = dalloc<float>(T);
+      sc_top_ = dalloc<int32_t>(T);
+      sc_topv_ = dalloc<float>(T);
+      sc_target_ = dalloc<int32_t>(T);
+    }
+    if (T > sc_T_ || Vc > sc_Vc_) {
+      const int t = std::max(T, sc_T_), v = std::max(Vc, sc_Vc_);
+      dfree(sc_logits_);
+      sc_logits_ = dalloc<float>((size_t)t * v);
+      if (hfmt_ != 0 && v > sc_Vc_) {
+        dfree(sc_head_);
+        sc_head_ = dalloc<uint16_t>((size_t)v * cfg_.H);
+      }
+      sc_T_ = t;
+      sc_Vc_ = v;
+    }
   }
 
   void gemm(int epi, const void* a, long long lda, const void* b, long long ldb, void* cptr,
@@ -3108,6 +3220,19 @@ CAKE_API int32_t cake_engine_forced_logits(void* h, const int32_t* prompt, int32
   try {
     if (!h || !prompt || (!forced && n_forced > 0) || !out) throw cake::Error("null argument");
     static_cast<Llama*>(h)->forced_logits(prompt, n_prompt, forced, n_forced, out);
+    return 0;
+  } catch (const std::exception& e) {
+    cake::put_err(err, errlen, e.what());
+    return 1;
+  }
+}
+
+CAKE_API int32_t cake_engine_score(void* h, const int32_t* tokens, int32_t n, int32_t vchunk,
+                                   float* lse, float* tgt, int32_t* top, float* topv, char* err,
+                                   int32_t errlen) {
+  try {
+    if (!h || !tokens || !lse || !tgt || !top || !topv) throw cake::Error("null argument");
+    static_cast<Llama*>(h)->score(tokens, n, vchunk, lse, tgt, top, topv);
     return 0;
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());

@@ -187,6 +187,17 @@ int32_t cake_engine_continue(void* engine, int32_t max_new, const int32_t* eos, 
 int32_t cake_engine_forced_logits(void* engine, const int32_t* prompt, int32_t n_prompt,
                                   const int32_t* forced, int32_t n_forced, float* out, char* err,
                                   int32_t errlen);
+// Teacher-forced scoring of tokens[0, n), 2 <= n <= max_seq: one prefill, then the head over
+// every row in vocabulary chunks reduced on the device ([n, V] logits never exist).  Row i is
+// the distribution after tokens[0..i]: lse[i] = log sum exp of its logits, tgt[i] the logit of
+// tokens[i + 1] (NaN on the last row), top[i] / topv[i] the argmax id (lowest at ties) and its
+// logit; log p(tokens[i + 1]) = tgt[i] - lse[i].  vchunk: chunk width in vocabulary ids, a
+// positive multiple of 256 (clamped to V), or 0 = the largest that keeps the f32 chunk within
+// 64 MB.  An engine that holds the head, not tensor parallel; any weight / head / KV /
+// prefill format.  Leaves the engine as cake_engine_prefill_logits does.
+int32_t cake_engine_score(void* engine, const int32_t* tokens, int32_t n, int32_t vchunk,
+                          float* lse, float* tgt, int32_t* top, float* topv, char* err,
+                          int32_t errlen);
 // "rank:first-last,..." layer runs of the token's walk (placement check); bytes written.
 int32_t cake_engine_walk(void* engine, char* out, int32_t cap);
 // Logits of the last prompt position after a prefill only (f32 [V] to host), for tests.

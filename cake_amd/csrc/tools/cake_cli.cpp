@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -118,6 +119,11 @@ const Flag kFlags[] = {
      "activations quantised per token to e4m3 and multiplied with the resident fp8 codes "
      "(needs --weight-dtype fp8; not with --parallel tp; each worker's own flag governs its own "
      "layers); model = the weights' own prefill"},
+    {"--score-file", "score_file", PyArg::kStr, nullptr, nullptr, false,
+     "native Llama engine: score this UTF-8 text file instead of generating: [bos] + its tokens "
+     "in consecutive windows of --max-seq-len, teacher forced; one JSON line {tokens, scored, "
+     "windows, nll, ppl, top1} on stdout (any --weight-dtype / --head-dtype / --kv-dtype / "
+     "--prefill-dtype; not with --parallel tp)"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -178,6 +184,8 @@ struct EngineApi {
   int32_t (*generate)(void*, const int32_t*, int32_t, int32_t, const CakeEngineSampling*,
                       const int32_t*, int32_t, cake_engine_token_cb, void*, int32_t*, int32_t,
                       CakeEngineStats*, char*, int32_t);
+  int32_t (*score)(void*, const int32_t*, int32_t, int32_t, float*, float*, int32_t*, float*,
+                   char*, int32_t);
   void (*close)(void*);
 };
 
@@ -268,6 +276,13 @@ int num_hidden_layers(const std::string& model_dir) {
 }
 
 int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
+  const bool scoring = o["score_file"].kind != PyArg::kNone;
+  if (scoring && o["transport"].value == "rccl" && o["parallel"].value == "tp") {
+    // every rank refuses alike, before the engine library loads
+    std::fprintf(stderr, "cake-cli: --score-file is not supported with --parallel tp: a "
+                         "tensor-parallel engine shards the vocabulary\n");
+    return 2;
+  }
   const std::string lib = cake::package_root() + "/cake_amd/lib/libcake_engine.so";
   void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!h) {
@@ -282,8 +297,9 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   api.serve = reinterpret_cast<decltype(api.serve)>(dlsym(h, "cake_engine_serve"));
   api.open_tp = reinterpret_cast<decltype(api.open_tp)>(dlsym(h, "cake_engine_open_tp"));
   api.open_remote = reinterpret_cast<decltype(api.open_remote)>(dlsym(h, "cake_engine_open_remote"));
+  api.score = reinterpret_cast<decltype(api.score)>(dlsym(h, "cake_engine_score"));
   if (!api.open || !api.generate || !api.close || !api.open_pp || !api.serve || !api.open_tp ||
-      !api.open_remote) {
+      !api.open_remote || !api.score) {
     std::fprintf(stderr, "cake-cli: engine symbols missing in %s\n", lib.c_str());
     return 1;
   }
@@ -333,6 +349,25 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     api.close(eng);
     return rc ? 1 : 0;
   }
+  std::vector<std::pair<int32_t, int32_t>> windows;  // --score-file: [start, end) token runs
+  if (scoring) {
+    try {
+      cake::Json req = cake::Json::object();
+      req.set("model", cake::Json::string(ctx.model));
+      req.set("path", cake::Json::string(o["score_file"].value));
+      req.set("max_seq", cake::Json::integer(o["max_seq_len"].kind == PyArg::kNone
+                                                 ? 4096
+                                                 : std::atoi(o["max_seq_len"].value.c_str())));
+      const cake::Json r = cake::Json::parse(
+          cake::call_python("cake_amd.native_bridge", "encode_score_file", req.dump()));
+      for (const auto& x : r.get("ids").items()) ids.push_back((int32_t)x.as_int());
+      for (const auto& w : r.get("windows").items())
+        windows.emplace_back((int32_t)w.items()[0].as_int(), (int32_t)w.items()[1].as_int());
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "cake-cli: --score-file: %s\n", e.what());
+      return 1;
+    }
+  } else
   try {
     cake::Json req = cake::Json::object();
     req.set("model", cake::Json::string(ctx.model));
@@ -397,6 +432,40 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   std::fprintf(stderr, "[cake-cli] native engine: model loaded in %.1f s (%zu prompt tokens)%s\n",
                load_s, ids.size(),
                worker_of.empty() ? "" : ", native master over TCP workers");
+  if (scoring) {
+    // each window from position 0 (its first token unscored); nll over all scored tokens
+    double nll_sum = 0.0;
+    long long scored = 0, hits = 0;
+    for (const auto& w : windows) {
+      const int32_t n = w.second - w.first;
+      std::vector<float> lse((size_t)n), tgt((size_t)n), topv((size_t)n);
+      std::vector<int32_t> top((size_t)n);
+      if (api.score(eng, ids.data() + w.first, n, 0, lse.data(), tgt.data(), top.data(),
+                    topv.data(), err, sizeof(err))) {
+        std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
+        api.close(eng);
+        return 1;
+      }
+      for (int32_t i = 0; i + 1 < n; ++i) {
+        nll_sum -= (double)tgt[(size_t)i] - (double)lse[(size_t)i];
+        hits += top[(size_t)i] == ids[(size_t)(w.first + i + 1)];
+      }
+      scored += n - 1;
+    }
+    api.close(eng);
+    const double nll = scored ? nll_sum / (double)scored : 0.0;
+    std::fprintf(stderr, "[cake-cli] %lld tokens scored in %zu window(s)\n", scored,
+                 windows.size());
+    if (!scored) {
+      std::fprintf(stderr, "cake-cli: --score-file: fewer than 2 tokens, nothing to score\n");
+      return 1;
+    }
+    std::printf("{\"tokens\": %zu, \"scored\": %lld, \"windows\": %zu, \"nll\": %.17g, "
+                "\"ppl\": %.17g, \"top1\": %.17g}\n", ids.size(), scored, windows.size(), nll,
+                std::exp(nll), (double)hits / (double)scored);
+    std::fflush(stdout);
+    return 0;
+  }
   CakeEngineSampling smp{};
   smp.temperature = (float)num("temperature", 1.0);
   smp.top_k = (int32_t)num("top_k", 0);

@@ -124,6 +124,10 @@ def lib() -> C.CDLL:
         L.cake_engine_prefill_logits.argtypes = [P, C.POINTER(C.c_int32), I,
                                                  C.POINTER(C.c_float), C.c_char_p, I]
         L.cake_engine_prefill_logits.restype = I
+        FP = C.POINTER(C.c_float)
+        L.cake_engine_score.argtypes = [P, C.POINTER(C.c_int32), I, I, FP, FP,
+                                        C.POINTER(C.c_int32), FP, C.c_char_p, I]
+        L.cake_engine_score.restype = I
         L.cake_engine_close.argtypes = [P]
         L.cake_engine_close.restype = None
         _lib = L
@@ -139,6 +143,31 @@ class GenResult:
     tokens_per_s: float = 0.0
     p50_ms: float = 0.0
     p99_ms: float = 0.0
+
+
+@dataclass
+class ScoreResult:
+    """Teacher-forced scores of ``n`` tokens (:meth:`NativeLlama.score`).  Row ``i`` is the
+    model's distribution after ``tokens[0..i]``; its target is ``tokens[i + 1]``."""
+    lse: "np.ndarray"            # float32 [n]: log sum exp of the row's logits
+    target_logit: "np.ndarray"   # float32 [n]: logit of tokens[i + 1]; NaN on the last row
+    top: "np.ndarray"            # int32 [n]: argmax id (the lowest at ties)
+    top_logit: "np.ndarray"      # float32 [n]: the logit there
+    logprobs: "np.ndarray"       # float64 [n - 1]: target_logit - lse
+    nll: float                   # mean of -logprobs
+    ppl: float                   # exp(nll)
+    top1: float                  # share of rows i < n - 1 with top[i] == tokens[i + 1]
+
+
+def score_result(tokens, lse, target_logit, top, top_logit) -> ScoreResult:
+    """The derived figures of one scored sequence from the engine's four arrays."""
+    import numpy as np
+    n = len(tokens)
+    logprobs = target_logit[:n - 1].astype(np.float64) - lse[:n - 1].astype(np.float64)
+    nll = float(-logprobs.mean())
+    hits = int(np.count_nonzero(top[:n - 1] == np.asarray(tokens[1:], dtype=np.int32)))
+    return ScoreResult(lse, target_logit, top, top_logit, logprobs, nll, float(np.exp(nll)),
+                       hits / (n - 1))
 
 
 class NativeLlama:
@@ -320,6 +349,34 @@ class NativeLlama:
         if rc:
             raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
         return out
+
+    def score(self, tokens: list[int], *, vchunk: int = 0) -> ScoreResult:
+        """Teacher-forced log-likelihood of ``tokens`` (2 <= n <= max_seq) from one prefill:
+        per-row log-sum-exp, target logit, argmax and its logit, reduced on the device one
+        vocabulary chunk at a time (``vchunk`` ids wide: a positive multiple of 256, or 0 =
+        as wide as a 64 MB f32 chunk allows), plus ``logprobs``, ``nll``, ``ppl`` and
+        ``top1``.  Works in every ``weights`` / ``head`` / ``kv`` / ``prefill`` mode, on a
+        single rank, rank 0 of a pipeline and a master with TCP workers; not with
+        ``tp=True`` nor on a ``layers`` engine.  The head here is a 16-bit GEMM over the
+        16-bit normalised rows (a quantised head is widened chunk by chunk), so the last
+        row differs from :meth:`prefill_logits`, whose head normalises in f32, by that
+        rounding."""
+        import numpy as np
+        n = len(tokens)
+        if n < 2:
+            raise ValueError("score: at least 2 tokens (the first token is never scored)")
+        arr = (C.c_int32 * n)(*[int(t) for t in tokens])
+        lse, tgt, topv = (np.empty(n, dtype=np.float32) for _ in range(3))
+        top = np.empty(n, dtype=np.int32)
+        err = C.create_string_buffer(1024)
+        fp = C.POINTER(C.c_float)
+        rc = lib().cake_engine_score(self._h, arr, n, int(vchunk), lse.ctypes.data_as(fp),
+                                     tgt.ctypes.data_as(fp),
+                                     top.ctypes.data_as(C.POINTER(C.c_int32)),
+                                     topv.ctypes.data_as(fp), err, len(err))
+        if rc:
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        return score_result(tokens, lse, tgt, top, topv)
 
     def forced_logits(self, prompt: list[int], forced: list[int]):
         """Teacher forcing: f32 logits [len(forced) + 1, V] after the prompt and after each

@@ -146,6 +146,23 @@ class NativeLLM(TextGenerator):
         return out
 
 
+def score_file(ctx, path: str) -> dict:
+    """``--score-file``: teacher-forced log-likelihood of a text file on the native engine,
+    in windows of ``--max-seq-len`` tokens (native_bridge.score_windows); the result line's
+    dict."""
+    from ...native_bridge import score_file_tokens, score_summary, score_windows
+    ids = score_file_tokens(str(ctx.model_path), path)
+    if len(ids) < 2:
+        raise RuntimeError("--score-file: fewer than 2 tokens, nothing to score")
+    llm = NativeLLM.load(ctx)
+    try:
+        parts = [(ids[a:b], llm.eng.score(ids[a:b]))
+                 for a, b in score_windows(len(ids), llm.eng.max_seq)]
+    finally:
+        llm.eng.close()
+    return score_summary(len(ids), parts)
+
+
 def _dtype_name(dtype) -> str:
     import torch
     if dtype == torch.bfloat16:

@@ -46,3 +46,44 @@ def decode_token(req: str) -> str:
         return tok.decode([int(r["id"])], skip_special_tokens=False) or ""
     except Exception:  # noqa: BLE001  (the generator streams nothing for such ids)
         return ""
+
+
+def score_windows(n_tokens: int, max_seq: int) -> list[tuple[int, int]]:
+    """[start, end) of the windows ``--score-file`` scores: consecutive runs of ``max_seq``
+    tokens, each scored from position 0 (its first token unscored); a last window of one
+    token has nothing to score and is dropped."""
+    if max_seq < 2:
+        raise ValueError("--score-file needs --max-seq-len >= 2")
+    return [(a, min(a + max_seq, n_tokens)) for a in range(0, n_tokens, max_seq)
+            if min(a + max_seq, n_tokens) - a >= 2]
+
+
+def score_file_tokens(model_dir: str, path: str) -> list[int]:
+    """``[bos] + encode(text)`` of a UTF-8 text file, no other special tokens."""
+    from .models.llama3.config import LlamaConfig
+    cfg = LlamaConfig.from_path(Path(model_dir))
+    if cfg.bos_token_id is None:
+        raise ValueError("--score-file: config.json names no bos_token_id")
+    tok, _ = _tokenizer(str(model_dir))
+    text = Path(path).read_text(encoding="utf-8")
+    return [int(cfg.bos_token_id), *tok.encode(text, add_special_tokens=False).ids]
+
+
+def encode_score_file(req: str) -> str:
+    """{"model", "path", "max_seq"} -> {"ids": [...], "windows": [[start, end], ...]}"""
+    r = json.loads(req)
+    ids = score_file_tokens(r["model"], r["path"])
+    return json.dumps({"ids": ids, "windows": score_windows(len(ids), int(r["max_seq"]))})
+
+
+def score_summary(n_tokens: int, parts: list) -> dict:
+    """The ``--score-file`` result line from the per-window (tokens, ScoreResult) pairs:
+    ``nll`` is the mean over all scored tokens."""
+    import math
+    scored = sum(len(t) - 1 for t, _ in parts)
+    total = sum(float(-r.logprobs.sum()) for _, r in parts)
+    hits = sum(round(r.top1 * (len(t) - 1)) for t, r in parts)
+    nll = total / scored if scored else float("nan")
+    return {"tokens": n_tokens, "scored": scored, "windows": len(parts), "nll": nll,
+            "ppl": math.exp(nll) if scored else float("nan"),
+            "top1": hits / scored if scored else float("nan")}

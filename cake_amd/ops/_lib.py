@@ -194,3 +194,8 @@ _SIGS.update({
     "cake_gemm_w8a8_plan": [I, I, I],
     "cake_gemm_w8a8_num_cfgs": [],
 })
+# sequence scoring: streaming log-sum-exp / target gather / argmax reducer (score.hip)
+_SIGS.update({
+    "cake_lse_rows": [P, C.c_longlong, I, I, I, I, P, P, P, P, P, P],
+    "cake_lse_finish": [P, P, P, I, P, P, P, P],
+})

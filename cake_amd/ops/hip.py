@@ -1481,3 +1481,43 @@ def to_rgb8(img, nhwc: bool = False) -> torch.Tensor:
     check(kernels().cake_to_rgb8(_dt(img), _p(img), B, H, W, int(nhwc), _p(out), _stream()),
           "to_rgb8")
     return out
+
+
+# ---------------------------------------------------------------------------
+# sequence scoring (score.hip)
+# ---------------------------------------------------------------------------
+
+def lse_rows(logits, v0: int, first: bool, target, run_max, run_sum, tgt, key):
+    """One vocabulary chunk of a streaming log-sum-exp / target gather / argmax: `logits`
+    f32 [T, Vc] (a view with any row stride and a unit column stride) holds the logits of
+    ids [v0, v0 + Vc).  State per row, started when `first`: run_max f32, run_sum f64
+    (sum exp(x - run_max)), tgt f32 (the logit of target[t], int32, -1 = none -> NaN), key
+    int64 holding the unsigned argmax key (ordered(x) << 32 | ~id)."""
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_cuda:
+        raise ValueError("lse_rows: logits must be a device float32 [T, Vc] tensor")
+    T, Vc = logits.shape
+    if Vc < 1 or T < 1 or logits.stride(1) != 1 or (T > 1 and logits.stride(0) < Vc):
+        raise ValueError("lse_rows: unit column stride and a row stride >= Vc expected")
+    _req(target, "target", dtype=torch.int32, shape=(T,))
+    _req(run_max, "run_max", dtype=torch.float32, shape=(T,))
+    _req(run_sum, "run_sum", dtype=torch.float64, shape=(T,))
+    _req(tgt, "tgt", dtype=torch.float32, shape=(T,))
+    _req(key, "key", dtype=torch.int64, shape=(T,))
+    ld = logits.stride(0) if T > 1 else max(Vc, logits.stride(0))
+    check(kernels().cake_lse_rows(_p(logits), ld, T, Vc, int(v0), int(bool(first)), _p(target),
+                                  _p(run_max), _p(run_sum), _p(tgt), _p(key), _stream()),
+          "lse_rows")
+
+
+def lse_finish(run_max, run_sum, key, lse, top, topv):
+    """lse = run_max + log(run_sum) (f64, stored f32; -inf for a row of -inf), top / topv =
+    the id and the logit the argmax key holds."""
+    T = run_max.numel()
+    _req(run_max, "run_max", dtype=torch.float32, shape=(T,))
+    _req(run_sum, "run_sum", dtype=torch.float64, shape=(T,))
+    _req(key, "key", dtype=torch.int64, shape=(T,))
+    _req(lse, "lse", dtype=torch.float32, shape=(T,))
+    _req(top, "top", dtype=torch.int32, shape=(T,))
+    _req(topv, "topv", dtype=torch.float32, shape=(T,))
+    check(kernels().cake_lse_finish(_p(run_max), _p(run_sum), _p(key), T, _p(lse), _p(top),
+                                    _p(topv), _stream()), "lse_finish")
