@@ -10,7 +10,10 @@
   when absent; on the device path they are read by the decode graph from device
   memory, no recapture), adds a ``usage`` block
   and lowercase ``role`` (``CAKE_API_REFERENCE_ROLES=1`` restores the
-  capitalised reference serialisation).
+  capitalised reference serialisation).  ``logprobs: true`` with ``top_logprobs`` in
+  [0, 20] (the native engine) adds ``choices[0].logprobs.content``: one entry per
+  emitted token, ``{token, id, logprob, bytes, top_logprobs: [{token, id, logprob,
+  bytes}]}``; a non-finite log-prob is sent as -9999.0.
 * ``POST /api/v1/image`` — body ``{"image_args": {...sd-* keys...}}``,
   returns ``{"images": [base64 PNG, ...]}`` (image.rs:15-68).
 * anything else → 404 with body ``nope`` (mod.rs:19-21,40).
@@ -61,6 +64,43 @@ def request_sampling(body: dict, default):
     return dataclasses.replace(default, **over)
 
 
+LOGPROBS_MAX_TOP = 20
+LOGPROB_FLOOR = -9999.0   # JSON has no -Infinity
+
+
+def request_logprobs(body: dict) -> int | None:
+    """The request's log-prob setting: None (not asked) or the number of alternatives per
+    token.  ValueError on an invalid combination."""
+    want = body.get("logprobs")
+    if want is not None and not isinstance(want, bool):
+        raise ValueError("logprobs must be a boolean")
+    top = body.get("top_logprobs")
+    if top is not None:
+        if isinstance(top, bool) or not isinstance(top, int) or not 0 <= top <= LOGPROBS_MAX_TOP:
+            raise ValueError(f"top_logprobs must be an integer in [0, {LOGPROBS_MAX_TOP}]")
+        if not want:
+            raise ValueError("top_logprobs needs logprobs: true")
+    return (top or 0) if want else None
+
+
+def logprob_entry(llm, tok) -> dict:
+    """One ``logprobs.content`` entry of an emitted Token."""
+    import math
+
+    def one(tid: int, lp, text=None) -> dict:
+        if text is None:
+            try:
+                text = llm.tokenizer.decode([tid], skip_special_tokens=False) or ""
+            except Exception:  # noqa: BLE001  (an id the tokenizer cannot render)
+                text = ""
+        v = float(lp) if lp is not None and math.isfinite(lp) else LOGPROB_FLOOR
+        return {"token": text, "id": int(tid), "logprob": v, "bytes": list(text.encode("utf-8"))}
+
+    e = one(tok.id, tok.logprob, tok.text or "")
+    e["top_logprobs"] = [one(i, lp) for i, lp in (tok.top_logprobs or [])]
+    return e
+
+
 def create_app(master):
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
@@ -92,20 +132,32 @@ def create_app(master):
                     check(sampling)  # a generator may support only part of the space
             except (TypeError, ValueError) as e:
                 return JSONResponse({"error": f"bad request: {e}"}, status_code=400)
+        try:
+            want_lp = request_logprobs(body)
+        except ValueError as e:
+            return JSONResponse({"error": f"bad request: {e}"}, status_code=400)
+        if want_lp is not None and not hasattr(master.llm, "set_logprobs"):
+            return JSONResponse({"error": "bad request: logprobs need the native engine (a "
+                                          "GPU, f16 / bf16, graphs on, CAKE_NATIVE != 0)"},
+                                status_code=400)
         model_name = master.llm.MODEL_NAME
         rid, created = str(uuid.uuid4()), int(time.time())
         role = "Assistant" if _reference_roles() else "assistant"
 
-        def run(sink):
+        def run(sink, on_token=None):
             with lock:
                 master.reset()
+                if hasattr(master.llm, "set_logprobs"):
+                    master.llm.set_logprobs(want_lp)
                 # a new configuration, or an explicit seed (restart its stream)
                 if sampling is not None and (body.get("seed") is not None or
                                              sampling != getattr(master.llm, "sampling", None)):
                     master.llm.set_sampling(sampling)
                 for m in messages:
                     master.llm.add_message(m)
-                return master.generate_text(sink, max_tokens=max_tokens)
+                if on_token is None:
+                    return master.generate_text(sink, max_tokens=max_tokens)
+                return master.generate_text(sink, max_tokens=max_tokens, on_token=on_token)
 
         if body.get("stream"):
             import queue
@@ -113,7 +165,12 @@ def create_app(master):
 
             def worker():
                 try:
-                    run(lambda s: q.put(s))
+                    if want_lp is None:
+                        run(lambda s: q.put(s))
+                    else:  # the text sink runs first: pair each text with its token's entry
+                        last: list[str] = []
+                        run(last.append,
+                            lambda t: q.put((last.pop(), logprob_entry(master.llm, t))))
                 finally:
                     q.put(None)
             threading.Thread(target=worker, daemon=True).start()
@@ -123,21 +180,33 @@ def create_app(master):
                     s = q.get()
                     if s is None:
                         break
+                    entry = None
+                    if want_lp is not None:
+                        s, entry = s
                     chunk = {"id": rid, "object": "chat.completion.chunk", "created": created,
                              "model": model_name,
                              "choices": [{"index": 0, "delta": {"content": s}, "finish_reason": None}]}
+                    if entry is not None:
+                        chunk["choices"][0]["logprobs"] = {"content": [entry]}
                     yield f"data: {json.dumps(chunk)}\n\n"
                 yield "data: [DONE]\n\n"
             return StreamingResponse(events(), media_type="text/event-stream")
 
         import anyio
         parts: list[str] = []
-        stats = await anyio.to_thread.run_sync(lambda: run(parts.append))
+        entries: list[dict] = []
+        if want_lp is None:
+            stats = await anyio.to_thread.run_sync(lambda: run(parts.append))
+        else:
+            stats = await anyio.to_thread.run_sync(lambda: run(
+                parts.append, lambda t: entries.append(logprob_entry(master.llm, t))))
         text = "".join(parts)
+        choice = {"index": 0, "message": {"role": role, "content": text}, "finish_reason": "stop"}
+        if want_lp is not None:
+            choice["logprobs"] = {"content": entries}
         return JSONResponse({
             "id": rid, "object": "chat.completion", "created": created, "model": model_name,
-            "choices": [{"index": 0, "message": {"role": role, "content": text},
-                         "finish_reason": "stop"}],
+            "choices": [choice],
             "usage": {"completion_tokens": stats.get("generated", 0)},
         })
 

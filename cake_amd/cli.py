@@ -111,6 +111,12 @@ def build_parser() -> argparse.ArgumentParser:
            "[bos] + its tokens in consecutive windows of --max-seq-len, teacher forced; one "
            "JSON line {tokens, scored, windows, nll, ppl, top1} on stdout (any --weight-dtype "
            "/ --head-dtype / --kv-dtype / --prefill-dtype; not with --parallel tp)")
+    a("--logprobs-file", default=None, metavar="PATH",
+      help="native Llama engine: write one JSON line per generated token to PATH: {index, id, "
+           "logprob, top_ids, top_logprobs}, over the logits token selection saw (after the "
+           "repeat penalty, before temperature / top-k / top-p); not with --parallel tp")
+    a("--top-logprobs", type=int, default=None, metavar="K",
+      help="with --logprobs-file: alternatives per token, 0..20 (0 when absent)")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -219,6 +225,33 @@ def score_file_refusal(ctx) -> str | None:
     return None
 
 
+def logprobs_file_refusal(ctx) -> str | None:
+    """Why this context cannot run ``--logprobs-file`` / ``--top-logprobs`` (None: it can, or
+    the options are off), in the wording of :func:`needs_native`."""
+    a = ctx.args
+    path, k = getattr(a, "logprobs_file", None), getattr(a, "top_logprobs", None)
+    if k is not None:
+        if not path:
+            return "--top-logprobs needs --logprobs-file"
+        if not 0 <= int(k) <= 20:
+            return f"--top-logprobs must be in [0, 20], got {k}"
+    if not path:
+        return None
+    native = ("--logprobs-file is served by the native Llama engine only (a GPU, --dtype f16 or "
+              "bf16, hipGraph decode, CAKE_NATIVE not 0)")
+    if ctx.model_type != "text-model":
+        return native + ": it applies to the text model only"
+    if a.transport == "rccl" and getattr(a, "parallel", "pp") == "tp":
+        return ("--logprobs-file is not supported with --parallel tp: a tensor-parallel engine "
+                "shards the vocabulary")
+    from .models.llama3.native_generator import native_eligible
+    if (not native_eligible(ctx) or a.transport != "tcp" or a.mode == "worker"
+            or getattr(a, "api", None)):
+        return native + ("; this run would take the Python path, which has no log-probs of "
+                         "generated tokens: refusing rather than generating without them")
+    return None
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -228,7 +261,8 @@ def _run(args) -> int:
     from .context import Context
     ctx = Context.from_args(args)
     why = (weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
-           or prefill_dtype_refusal(ctx) or score_file_refusal(ctx))
+           or prefill_dtype_refusal(ctx) or score_file_refusal(ctx)
+           or logprobs_file_refusal(ctx))
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

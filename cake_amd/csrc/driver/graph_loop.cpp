@@ -11,6 +11,7 @@
 //   * replay the step graph whose decode-attention split cap covers the live
 //     length (one graph per position bucket, chosen through a host table),
 //   * copy the replay's k tokens from the device history into a pinned ring and
+//     (with the per-token records of CakeLoopSpec.rec next to them, when asked) and
 //     record an event — and only then wait for the PREVIOUS replay's event, so
 //     the GPU always has the next step queued while the host reads one back,
 //   * stop at EOS, at n tokens, or when the per-token callback asks (streaming
@@ -24,6 +25,7 @@
 #include <stdint.h>
 
 #include <chrono>
+#include <cstring>
 #include <vector>
 
 #define CAKE_API extern "C" __attribute__((visibility("default")))
@@ -40,12 +42,14 @@ namespace {
 struct Ring {
   int32_t* host = nullptr;
   int cap = 0;  // int32 slots
+  uint8_t* rec = nullptr;  // per-token records next to the tokens (CakeLoopSpec.rec)
+  size_t rec_cap = 0;      // bytes
   int dev = -1;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 thread_local Ring t_ring;
 
-hipError_t ring_for(int slots, Ring*& out) {
+hipError_t ring_for(int slots, size_t rec_bytes, Ring*& out) {
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -66,6 +70,14 @@ hipError_t ring_for(int slots, Ring*& out) {
         hipSuccess)
       return e;
     r.cap = slots;
+  }
+  if (r.rec_cap < rec_bytes) {  // grown once, as the token slots are
+    if (r.rec) (void)hipHostFree(r.rec);
+    r.rec = nullptr;
+    r.rec_cap = 0;
+    if ((e = hipHostMalloc((void**)&r.rec, rec_bytes, hipHostMallocDefault)) != hipSuccess)
+      return e;
+    r.rec_cap = rec_bytes;
   }
   out = &r;
   return hipSuccess;
@@ -93,6 +105,10 @@ CAKE_API int cake_graph_decode(const CakeLoopSpec* s, CakeLoopResult* r) {
   const int replays = (s->n + k - 1) / k;
   const bool readback = s->hist != nullptr;
   if (readback && (!s->out_tokens || s->out_cap < s->n)) return (int)hipErrorInvalidValue;
+  // per-token records travel with the tokens (rec_bytes 0: none)
+  const size_t rb = s->rec_bytes > 0 ? (size_t)s->rec_bytes : 0;
+  if (s->rec_bytes < 0 || (rb && (!readback || !s->rec || !s->out_rec)))
+    return (int)hipErrorInvalidValue;
   const int chunk = s->chunk > 0 ? s->chunk : replays;
   int pos = s->pos;
   // one replay of the graph whose attention split cap covers the live length at its
@@ -118,7 +134,7 @@ CAKE_API int cake_graph_decode(const CakeLoopSpec* s, CakeLoopResult* r) {
   // other); three replay events (p+1 is recorded while p-1's still bounds p's
   // interval) and a start event
   Ring* rp = nullptr;
-  CAKE_TRY(ring_for(2 * k, rp));
+  CAKE_TRY(ring_for(2 * k, 2 * k * rb, rp));
   Ring& ring = *rp;
   CAKE_TRY(hipEventRecord(ring.ev[3], st));
   hipEvent_t prev_done = ring.ev[3];
@@ -152,6 +168,10 @@ CAKE_API int cake_graph_decode(const CakeLoopSpec* s, CakeLoopResult* r) {
         const int lo = s->base + issued * k;
         CAKE_LOOP_TRY(hipMemcpyAsync(ring.host + slot * k, s->hist + lo, sizeof(int32_t) * k,
                                      hipMemcpyDeviceToHost, st));
+        if (rb)
+          CAKE_LOOP_TRY(hipMemcpyAsync(ring.rec + (size_t)slot * k * rb,
+                                       static_cast<const uint8_t*>(s->rec) + (size_t)lo * rb,
+                                       rb * k, hipMemcpyDeviceToHost, st));
       }
       CAKE_LOOP_TRY(hipEventRecord(ring.ev[issued % 3], st));
       cur = issued++;
@@ -171,6 +191,9 @@ CAKE_API int cake_graph_decode(const CakeLoopSpec* s, CakeLoopResult* r) {
         if (readback) {
           const int32_t tok = ring.host[slot * k + i];
           s->out_tokens[idx] = tok;
+          if (rb)  // before on_token, which may read it
+            std::memcpy(static_cast<uint8_t*>(s->out_rec) + (size_t)idx * rb,
+                        ring.rec + (size_t)(slot * k + i) * rb, rb);
           r->n_tokens = idx + 1;
           if (s->on_token && s->on_token(s->token_ctx, tok) != 0) stop = true;
           for (int e = 0; e < s->n_eos && !stop; ++e)

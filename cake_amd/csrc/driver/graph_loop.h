@@ -29,6 +29,9 @@ struct CakeLoopSpec {
   int32_t* out_tokens;        // host [out_cap]
   float* out_ms;              // host [out_cap]: device time per token (ms)
   int32_t out_cap;
+  const void* rec;            // device per-token records, indexed like hist (or null)
+  int32_t rec_bytes;          // bytes per record; 0: no records
+  void* out_rec;              // host [out_cap * rec_bytes]: filled before on_token sees the token
 };
 
 struct CakeLoopResult {

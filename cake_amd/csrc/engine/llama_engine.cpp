@@ -105,6 +105,11 @@ int cake_lse_rows(const float* logits, long long ld, int T, int Vc, int v0, int 
                   unsigned long long* key, hipStream_t st);
 int cake_lse_finish(const float* run_max, const double* run_sum, const unsigned long long* key,
                     int T, float* lse, int32_t* top, float* topv, hipStream_t st);
+// log-probs of a generated token (logprob.hip): one 192-byte record at rec[*hist_len - 1]
+int cake_logprob_topk(const float* logits, int V, const int32_t* tok, const int32_t* hist_len,
+                      int K, void* rec, int max_rec, void* ws, unsigned int* ticket,
+                      int max_blocks, hipStream_t st);
+long long cake_logprob_ws_bytes(int V);
 // MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
 int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void* e8,
                           hipStream_t st);
@@ -688,6 +693,52 @@ class Llama {
     check_attn_error("rank " + std::to_string(rank()));
   }
 
+  // Log-probs of the generated tokens, from the next generate() on: top_k < 0 off (the
+  // default), 0..20 on with that many alternatives per token.  The record array [max_seq],
+  // the partials workspace and the ticket are allocated at the first call that turns it on.
+  void set_logprobs(int top_k) {
+    hip_check(hipSetDevice(dev_), "hipSetDevice");
+    if (top_k > kLpMaxTop)
+      throw Error("log-probs: at most " + std::to_string(kLpMaxTop) +
+                  " alternatives per token, got " + std::to_string(top_k));
+    if (top_k >= 0 && tp_ > 1)
+      throw Error("log-probs are not available on a tensor-parallel engine (the vocabulary is "
+                  "sharded)");
+    if (top_k >= 0 && !head_)
+      throw Error("log-probs need an engine that holds the head (pipeline rank 0)");
+    if (top_k >= 0 && !lp_rec_) {
+      lp_rec_ = dalloc<uint32_t>((size_t)S_ * kLpRecWords);
+      lp_ws_ = dalloc<uint8_t>((size_t)cake_logprob_ws_bytes(lc_.V));
+      lp_ticket_ = dalloc<unsigned int>(4);
+      hip_check(hipMemsetAsync(lp_rec_, 0, sizeof(uint32_t) * (size_t)S_ * kLpRecWords, st_),
+                "memset");
+      hip_check(hipMemsetAsync(lp_ticket_, 0, 16, st_), "memset");
+      hip_check(hipStreamSynchronize(st_), "sync");
+    }
+    lp_k_ = top_k < 0 ? -1 : top_k;
+  }
+
+  // Records of tokens [first, first + count) of the last generate() / continue() call, from
+  // the host copy (inside the token callback: every token reported so far, the current one
+  // included).  top_ids / top_logits are [count, 20]; entries past the call's top_k are id -1,
+  // logit -inf.
+  void logprobs(int first, int count, int32_t* ids, float* logit, float* lse, int32_t* top_ids,
+                float* top_logits) const {
+    if (!lp_on_) throw Error("the last generation ran without log-probs (set_logprobs)");
+    if (first < 0 || count < 0 || first + count > lp_n_)
+      throw Error("log-probs of tokens [" + std::to_string(first) + ", " +
+                  std::to_string(first + count) + ") asked, " + std::to_string(lp_n_) +
+                  " generated");
+    for (int i = 0; i < count; ++i) {
+      const uint32_t* r = lp_host_.data() + (size_t)(first + i) * kLpRecWords;
+      ids[i] = (int32_t)r[0];
+      std::memcpy(logit + i, r + 1, 4);
+      std::memcpy(lse + i, r + 2, 4);
+      std::memcpy(top_ids + (size_t)i * kLpMaxTop, r + 4, 4 * kLpMaxTop);
+      std::memcpy(top_logits + (size_t)i * kLpMaxTop, r + 4 + kLpMaxTop, 4 * kLpMaxTop);
+    }
+  }
+
   void generate(const int32_t* prompt, int T, int max_new, const CakeEngineSampling& smp,
                 const int32_t* eos, int n_eos, cake_engine_token_cb cb, void* ctx, int32_t* out,
                 int out_cap, CakeEngineStats* stats) {
@@ -734,6 +785,7 @@ class Llama {
       m.set("eos", eos_json(eos, n_eos));
       for (int fd : peers_) send_json(fd, m);
     }
+    lp_begin(last_mode_.logprobs >= 0, max_new);
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<float> ms;
     const int n_out = remote_mode()
@@ -760,6 +812,24 @@ class Llama {
     auto* t = static_cast<TpStop*>(vctx);
     if (!t->stopped && t->cb && t->cb(t->ctx, tok) != 0) t->stopped = true;
     return 0;
+  }
+
+  // counts a token's record as readable (cake_engine_logprobs) before the caller sees it
+  struct LpCb {
+    Llama* self;
+    cake_engine_token_cb cb;
+    void* ctx;
+  };
+  static int32_t lp_token_cb(void* vctx, int32_t tok) {
+    auto* c = static_cast<LpCb*>(vctx);
+    ++c->self->lp_n_;
+    return c->cb ? c->cb(c->ctx, tok) : 0;
+  }
+  // host copy of this call's records: room for max_new of them, none yet
+  void lp_begin(bool on, int max_new) {
+    lp_on_ = on;
+    lp_n_ = 0;
+    if (lp_on_) lp_host_.assign((size_t)max_new * kLpRecWords, 0u);
   }
 
   static Json eos_json(const int32_t* eos, int n_eos) {
@@ -800,6 +870,14 @@ class Llama {
     spec.out_tokens = toks.data();
     spec.out_ms = ms.data();
     spec.out_cap = n;
+    LpCb lpc{this, cb, ctx};
+    if (lp_on_ && lead) {  // the records ride the read-back ring with their tokens
+      spec.rec = lp_rec_;
+      spec.rec_bytes = kLpRecWords * 4;
+      spec.out_rec = lp_host_.data() + (size_t)lp_n_ * kLpRecWords;
+      spec.on_token = &Llama::lp_token_cb;
+      spec.token_ctx = &lpc;
+    }
     TpStop tps{cb, ctx, false};
     if (tp_ > 1) {  // lock step: every rank reads the tokens back and stops at EOS
       spec.on_token = lead ? &Llama::tp_token_cb : nullptr;
@@ -860,11 +938,17 @@ class Llama {
     } else {
       head_gemv(hidden_ + (size_t)(T - 1) * cfg_.H);
       select_tail(mode);
+      logprob_record(mode);
     }
     if (mode.fused) k_check(cake_embed(dt_, embed_, tok_, 1, cfg_.H, resid_, st_), "embed");
     int32_t first = 0;
     hip_check(hipMemcpyAsync(&first, tok_, sizeof(int32_t), hipMemcpyDeviceToHost, st_), "tok");
+    lp_begin(mode.logprobs >= 0, max_new);
+    if (lp_on_)  // the first token sits at history index T
+      hip_check(hipMemcpyAsync(lp_host_.data(), lp_rec_ + (size_t)T * kLpRecWords,
+                               kLpRecWords * 4, hipMemcpyDeviceToHost, st_), "logprob D2H");
     hip_check(hipStreamSynchronize(st_), "sync");
+    if (lp_on_ && lead) lp_n_ = 1;
     const auto t1 = std::chrono::steady_clock::now();
     int n_out = 0;
     bool stop = false;
@@ -932,10 +1016,12 @@ class Llama {
     float temperature = 0.f, top_p = 0.f, penalty = 1.f;
     int top_k = 0, last_n = 0;
     unsigned long long seed = 0;
+    int logprobs = -1;  // >= 0: a log-prob record per token with that many alternatives
     bool operator==(const Mode& o) const {
-      return std::tie(fused, greedy, temperature, top_p, penalty, top_k, last_n, seed) ==
+      return std::tie(fused, greedy, temperature, top_p, penalty, top_k, last_n, seed,
+                      logprobs) ==
              std::tie(o.fused, o.greedy, o.temperature, o.top_p, o.penalty, o.top_k, o.last_n,
-                      o.seed);
+                      o.seed, o.logprobs);
     }
   };
 
@@ -1068,6 +1154,16 @@ class Llama {
   unsigned long long* sc_key_ = nullptr;
   int32_t *sc_target_ = nullptr, *sc_top_ = nullptr;
   uint16_t* sc_head_ = nullptr;
+  // log-probs of generated tokens (set_logprobs): device records indexed like hist_, the
+  // kernel's partials and ticket; the host copy holds the last call's records in token order
+  static constexpr int kLpMaxTop = 20, kLpRecWords = 48;
+  int lp_k_ = -1;       // the next generate()'s setting
+  bool lp_on_ = false;  // the last generate() / continue() call recorded
+  int lp_n_ = 0;        // its records readable so far
+  uint32_t* lp_rec_ = nullptr;
+  uint8_t* lp_ws_ = nullptr;
+  unsigned int* lp_ticket_ = nullptr;
+  std::vector<uint32_t> lp_host_;
   float* ws_ = nullptr;
   size_t ws_n_ = 0;
   static constexpr size_t kLibWsBytes = 32u << 20;
@@ -1794,6 +1890,7 @@ class Llama {
       m.seed = s.seed;
     }
     m.fused = m.greedy && (m.penalty == 1.f || m.last_n <= kHeadSelectMaxLastN) && tp_ == 1;
+    m.logprobs = lp_k_;
     return m;
   }
 
@@ -1812,6 +1909,14 @@ class Llama {
                                  restrict ? thr_ : nullptr, slot_, st_), "gumbel_argmax");
     }
     k_check(cake_finalize_token(slot_, tok_, hist_, hist_len_, pos_, S_, st_), "finalize");
+  }
+
+  // the record of the token just finalised: logits_ still holds the row selection saw (the
+  // penalised values on every path), tok_ and hist_len_ the new values
+  void logprob_record(const Mode& m) {
+    if (m.logprobs < 0) return;
+    k_check(cake_logprob_topk(logits_, lc_.V, tok_, hist_len_, m.logprobs, lp_rec_, S_, lp_ws_,
+                              lp_ticket_, 0, st_), "logprob_topk");
   }
 
   // one decode step of this rank: its stops of the walk in order — receive (when the
@@ -2003,10 +2108,12 @@ class Llama {
                                  hist_, hist_len_, last_n, m.penalty, slot_, sel_ticket_, tok_,
                                  pos_, S_, embed_, resid_, st_),
                 "head_select");
+      logprob_record(m);
       return;
     }
     head_gemv(resid_);
     select_tail(m);
+    logprob_record(m);
   }
 
   // logits_ = lm_head . rms_norm(row): the 16-bit head or its quantised twin (head_fmt)
@@ -2219,7 +2326,18 @@ class Llama {
       short_step_ = false;
       int32_t tok = 0;
       hip_check(hipMemcpyAsync(&tok, tok_, sizeof(tok), hipMemcpyDeviceToHost, st_), "tok");
+      if (lp_on_) {  // the step's record: history index pos + 1 = pos0 + i + 1
+        if ((size_t)(lp_n_ + 1) * kLpRecWords > lp_host_.size()) throw Error("log-prob copy overrun");
+        int32_t hl = 0;
+        hip_check(hipMemcpyAsync(&hl, hist_len_, sizeof(hl), hipMemcpyDeviceToHost, st_), "len");
+        hip_check(hipStreamSynchronize(st_), "sync");
+        if (hl < 1 || hl > S_) throw Error("log-probs: history length out of range");
+        hip_check(hipMemcpyAsync(lp_host_.data() + (size_t)lp_n_ * kLpRecWords,
+                                 lp_rec_ + (size_t)(hl - 1) * kLpRecWords, kLpRecWords * 4,
+                                 hipMemcpyDeviceToHost, st_), "logprob D2H");
+      }
       hip_check(hipStreamSynchronize(st_), "sync");
+      if (lp_on_) ++lp_n_;
       ms.push_back((float)(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0)
                                .count() * 1e3));
       if (n_out < out_cap) out[n_out++] = tok;
@@ -3233,6 +3351,31 @@ CAKE_API int32_t cake_engine_score(void* h, const int32_t* tokens, int32_t n, in
   try {
     if (!h || !tokens || !lse || !tgt || !top || !topv) throw cake::Error("null argument");
     static_cast<Llama*>(h)->score(tokens, n, vchunk, lse, tgt, top, topv);
+    return 0;
+  } catch (const std::exception& e) {
+    cake::put_err(err, errlen, e.what());
+    return 1;
+  }
+}
+
+CAKE_API int32_t cake_engine_set_logprobs(void* h, int32_t top_k, char* err, int32_t errlen) {
+  try {
+    if (!h) throw cake::Error("null engine");
+    static_cast<Llama*>(h)->set_logprobs(top_k);
+    return 0;
+  } catch (const std::exception& e) {
+    cake::put_err(err, errlen, e.what());
+    return 1;
+  }
+}
+
+CAKE_API int32_t cake_engine_logprobs(void* h, int32_t first, int32_t count, int32_t* ids,
+                                      float* logit, float* lse, int32_t* top_ids,
+                                      float* top_logits, char* err, int32_t errlen) {
+  try {
+    if (!h || ((!ids || !logit || !lse || !top_ids || !top_logits) && count > 0))
+      throw cake::Error("null argument");
+    static_cast<Llama*>(h)->logprobs(first, count, ids, logit, lse, top_ids, top_logits);
     return 0;
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());

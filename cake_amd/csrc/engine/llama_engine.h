@@ -198,6 +198,22 @@ int32_t cake_engine_forced_logits(void* engine, const int32_t* prompt, int32_t n
 int32_t cake_engine_score(void* engine, const int32_t* tokens, int32_t n, int32_t vchunk,
                           float* lse, float* tgt, int32_t* top, float* topv, char* err,
                           int32_t errlen);
+// Log-probs of generated tokens.  top_k < 0: off (the default); 0..20: on, with that many
+// alternatives per token.  Takes effect at the next cake_engine_generate; a continue keeps
+// the setting of the generation it continues.  Per token, one launch inside the decode step
+// reads the f32 row token selection saw (after the repeat penalty, before temperature /
+// top-k / top-p / the draw) and writes a 192-byte record that the read-back ring carries to
+// the host with the token.  Refused: a tensor-parallel engine, an engine without the head,
+// top_k > 20.  The device buffers are allocated at the first call that turns it on.
+int32_t cake_engine_set_logprobs(void* engine, int32_t top_k, char* err, int32_t errlen);
+// Records of tokens [first, first + count) of the last generate / continue call (inside the
+// token callback: any token reported so far, the current one included): ids[count],
+// logit[count] = x[id] bit for bit, lse[count] = log sum exp x (f32; the caller forms
+// logprob = (double)logit - (double)lse), top_ids / top_logits [count, 20]: the top_k largest
+// logits, descending, the lower id first at ties; entries past min(top_k, V): id -1, -inf.
+int32_t cake_engine_logprobs(void* engine, int32_t first, int32_t count, int32_t* ids,
+                             float* logit, float* lse, int32_t* top_ids, float* top_logits,
+                             char* err, int32_t errlen);
 // "rank:first-last,..." layer runs of the token's walk (placement check); bytes written.
 int32_t cake_engine_walk(void* engine, char* out, int32_t cap);
 // Logits of the last prompt position after a prefill only (f32 [V] to host), for tests.

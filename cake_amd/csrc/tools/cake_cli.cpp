@@ -124,6 +124,12 @@ const Flag kFlags[] = {
      "in consecutive windows of --max-seq-len, teacher forced; one JSON line {tokens, scored, "
      "windows, nll, ppl, top1} on stdout (any --weight-dtype / --head-dtype / --kv-dtype / "
      "--prefill-dtype; not with --parallel tp)"},
+    {"--logprobs-file", "logprobs_file", PyArg::kStr, nullptr, nullptr, false,
+     "native Llama engine: write one JSON line per generated token to PATH: {index, id, logprob, "
+     "top_ids, top_logprobs}, over the logits token selection saw (after the repeat penalty, "
+     "before temperature / top-k / top-p); not with --parallel tp"},
+    {"--top-logprobs", "top_logprobs", PyArg::kInt, nullptr, nullptr, false,
+     "with --logprobs-file: alternatives per token, 0..20 (0 when absent)"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -186,6 +192,9 @@ struct EngineApi {
                       CakeEngineStats*, char*, int32_t);
   int32_t (*score)(void*, const int32_t*, int32_t, int32_t, float*, float*, int32_t*, float*,
                    char*, int32_t);
+  int32_t (*set_logprobs)(void*, int32_t, char*, int32_t);
+  int32_t (*logprobs)(void*, int32_t, int32_t, int32_t*, float*, float*, int32_t*, float*, char*,
+                      int32_t);
   void (*close)(void*);
 };
 
@@ -283,6 +292,14 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
                          "tensor-parallel engine shards the vocabulary\n");
     return 2;
   }
+  const bool lp_on = o["logprobs_file"].kind != PyArg::kNone;
+  const int32_t lp_k = o["top_logprobs"].kind == PyArg::kNone
+                           ? 0 : (int32_t)std::atoi(o["top_logprobs"].value.c_str());
+  if (lp_on && o["transport"].value == "rccl" && o["parallel"].value == "tp") {
+    std::fprintf(stderr, "cake-cli: --logprobs-file is not supported with --parallel tp: a "
+                         "tensor-parallel engine shards the vocabulary\n");
+    return 2;
+  }
   const std::string lib = cake::package_root() + "/cake_amd/lib/libcake_engine.so";
   void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!h) {
@@ -298,8 +315,11 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   api.open_tp = reinterpret_cast<decltype(api.open_tp)>(dlsym(h, "cake_engine_open_tp"));
   api.open_remote = reinterpret_cast<decltype(api.open_remote)>(dlsym(h, "cake_engine_open_remote"));
   api.score = reinterpret_cast<decltype(api.score)>(dlsym(h, "cake_engine_score"));
+  api.set_logprobs =
+      reinterpret_cast<decltype(api.set_logprobs)>(dlsym(h, "cake_engine_set_logprobs"));
+  api.logprobs = reinterpret_cast<decltype(api.logprobs)>(dlsym(h, "cake_engine_logprobs"));
   if (!api.open || !api.generate || !api.close || !api.open_pp || !api.serve || !api.open_tp ||
-      !api.open_remote || !api.score) {
+      !api.open_remote || !api.score || !api.set_logprobs || !api.logprobs) {
     std::fprintf(stderr, "cake-cli: engine symbols missing in %s\n", lib.c_str());
     return 1;
   }
@@ -478,6 +498,21 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   const int32_t max_new = n < room ? n : room;
   std::vector<int32_t> out((size_t)(max_new > 0 ? max_new : 1));
   CakeEngineStats st{};
+  std::FILE* lp_file = nullptr;
+  if (lp_on) {
+    if (api.set_logprobs(eng, lp_k, err, sizeof(err))) {
+      std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
+      api.close(eng);
+      return 1;
+    }
+    lp_file = std::fopen(o["logprobs_file"].value.c_str(), "w");
+    if (!lp_file) {
+      std::fprintf(stderr, "cake-cli: --logprobs-file: cannot write %s\n",
+                   o["logprobs_file"].value.c_str());
+      api.close(eng);
+      return 1;
+    }
+  }
   const int32_t rc = api.generate(eng, ids.data(), (int32_t)ids.size(), max_new, &smp,
                                   ctx.eos.data(), (int32_t)ctx.eos.size(), stream_token, &ctx,
                                   out.data(), (int32_t)out.size(), &st, err, sizeof(err));
@@ -487,6 +522,39 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
     api.close(eng);
     return 1;
+  }
+  if (rc != 0 && lp_file) std::fclose(lp_file);
+  if (rc == 0 && lp_file) {  // one line per generated token (EOS included)
+    const size_t n = (size_t)st.n_generated;
+    std::vector<int32_t> lid(n), tid(n * 20);
+    std::vector<float> lg(n), lse(n), tlg(n * 20);
+    if (api.logprobs(eng, 0, (int32_t)n, lid.data(), lg.data(), lse.data(), tid.data(),
+                     tlg.data(), err, sizeof(err))) {
+      std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
+      std::fclose(lp_file);
+      api.close(eng);
+      return 1;
+    }
+    // logprob = logit - lse in double; -inf for a -inf logit (JSON: -Infinity)
+    const auto put = [&](float logit, float l) {
+      const double v = std::isinf(logit) && logit < 0 ? -INFINITY : (double)logit - (double)l;
+      if (std::isfinite(v)) std::fprintf(lp_file, "%.17g", v);
+      else std::fputs(v < 0 ? "-Infinity" : (v > 0 ? "Infinity" : "NaN"), lp_file);
+    };
+    for (size_t i = 0; i < n; ++i) {
+      std::fprintf(lp_file, "{\"index\": %zu, \"id\": %d, \"logprob\": ", i, lid[i]);
+      put(lg[i], lse[i]);
+      std::fputs(", \"top_ids\": [", lp_file);
+      for (int32_t j = 0; j < lp_k; ++j)
+        std::fprintf(lp_file, "%s%d", j ? ", " : "", tid[i * 20 + (size_t)j]);
+      std::fputs("], \"top_logprobs\": [", lp_file);
+      for (int32_t j = 0; j < lp_k; ++j) {
+        if (j) std::fputs(", ", lp_file);
+        put(tlg[i * 20 + (size_t)j], lse[i]);
+      }
+      std::fputs("]}\n", lp_file);
+    }
+    std::fclose(lp_file);
   }
   std::fprintf(stderr, "[cake-cli] %d tokens generated (%.2f token/s) p50=%.2fms p99=%.2fms "
                "ttft=%.1fms\n", st.n_generated, st.tokens_per_s, st.p50_ms, st.p99_ms,
@@ -592,6 +660,18 @@ int main(int argc, char** argv) {
       continue;
     }
     opts[f->dest] = PyArg{f->kind, val};
+  }
+  // --logprobs-file / --top-logprobs: the flag pair itself, before anything starts
+  if (opts["top_logprobs"].kind != PyArg::kNone) {
+    if (opts["logprobs_file"].kind == PyArg::kNone) {
+      std::fprintf(stderr, "cake-cli: --top-logprobs needs --logprobs-file\n");
+      return 2;
+    }
+    const long long k = std::strtoll(opts["top_logprobs"].value.c_str(), nullptr, 10);
+    if (k < 0 || k > 20) {
+      std::fprintf(stderr, "cake-cli: --top-logprobs must be in [0, 20], got %lld\n", k);
+      return 2;
+    }
   }
   // ---- topology (native parser): validate placement before any runtime starts
   const bool text = opts["model_type"].value == "text-model";

@@ -128,6 +128,11 @@ def lib() -> C.CDLL:
         L.cake_engine_score.argtypes = [P, C.POINTER(C.c_int32), I, I, FP, FP,
                                         C.POINTER(C.c_int32), FP, C.c_char_p, I]
         L.cake_engine_score.restype = I
+        IP = C.POINTER(C.c_int32)
+        L.cake_engine_set_logprobs.argtypes = [P, I, C.c_char_p, I]
+        L.cake_engine_set_logprobs.restype = I
+        L.cake_engine_logprobs.argtypes = [P, I, I, IP, FP, FP, IP, FP, C.c_char_p, I]
+        L.cake_engine_logprobs.restype = I
         L.cake_engine_close.argtypes = [P]
         L.cake_engine_close.restype = None
         _lib = L
@@ -143,6 +148,43 @@ class GenResult:
     tokens_per_s: float = 0.0
     p50_ms: float = 0.0
     p99_ms: float = 0.0
+    logprobs: "TokenLogprobs | None" = None   # generate(..., logprobs=K)
+
+
+LOGPROBS_MAX_TOP = 20
+
+
+@dataclass
+class TokenLogprobs:
+    """Log-probs of ``n`` generated tokens (``NativeLlama.generate(..., logprobs=K)``), over
+    the f32 row token selection saw: after the repeat penalty, before temperature, top-k /
+    top-p and the draw (with ``repeat_penalty=1`` the model's own distribution)."""
+    ids: "np.ndarray"            # int32 [n]: the generated tokens
+    logit: "np.ndarray"          # float32 [n]: x[id], bit for bit
+    lse: "np.ndarray"            # float32 [n]: log sum exp of the row
+    logprob: "np.ndarray"        # float64 [n]: logit - lse (-inf for a -inf logit)
+    top_ids: "np.ndarray"        # int32 [n, K]: the K largest logits' ids, descending, the
+    top_logits: "np.ndarray"     # float32 [n, K]   lower id first at ties; past V: -1 / -inf
+    top_logprobs: "np.ndarray"   # float64 [n, K]
+
+
+def logprob_json_lines(lp: "TokenLogprobs") -> list[str]:
+    """The ``--logprobs-file`` lines of a generation: one JSON object per generated token,
+    ``{index, id, logprob, top_ids, top_logprobs}`` (a -inf log-prob as ``-Infinity``)."""
+    import json
+    return [json.dumps({"index": i, "id": int(lp.ids[i]), "logprob": float(lp.logprob[i]),
+                        "top_ids": [int(t) for t in lp.top_ids[i]],
+                        "top_logprobs": [float(v) for v in lp.top_logprobs[i]]}) + "\n"
+            for i in range(len(lp.ids))]
+
+
+def _logprob(logit, lse):
+    """float64 logit - lse, -inf where the logit is -inf (an all -inf row has lse -inf)."""
+    import numpy as np
+    l64 = np.asarray(logit, dtype=np.float64)
+    s64 = np.asarray(lse, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isneginf(l64), -np.inf, l64 - s64)
 
 
 @dataclass
@@ -397,7 +439,13 @@ class NativeLlama:
                  top_k: int | None = None, top_p: float | None = None, seed: int = 299792458,
                  repeat_penalty: float = 1.1, repeat_last_n: int = 128,
                  eos_ids: list[int] | None = None,
-                 on_token: Callable[[int], bool | None] | None = None) -> GenResult:
+                 on_token: Callable[[int], bool | None] | None = None,
+                 logprobs: int | None = None) -> GenResult:
+        """``logprobs``: None = off; K in [0, 20] = a log-prob record per generated token with
+        the K most likely alternatives (:class:`TokenLogprobs` in ``GenResult.logprobs``; inside
+        ``on_token``, :meth:`token_logprob`).  The tokens are the same either way.  Not with
+        ``tp=True`` nor on a ``layers`` engine."""
+        self.set_logprobs(logprobs)
         arr = (C.c_int32 * len(prompt))(*prompt)
         smp = EngineSampling(float(temperature or 0.0), int(top_k or 0), float(top_p or 0.0),
                              int(seed) & 0xFFFFFFFFFFFFFFFF, float(repeat_penalty),
@@ -406,15 +454,56 @@ class NativeLlama:
             self._h, arr, len(prompt), int(max_new), C.byref(smp), eos_arr, n_eos, cb, None, out,
             max(1, max_new), stats, err, len(err)), max_new, eos_ids, on_token)
 
+    def set_logprobs(self, k: int | None) -> None:
+        """The log-prob setting of the next :meth:`generate` (None: off, 0..20: on)."""
+        want = -1 if k is None else int(k)
+        if k is not None and not 0 <= want <= LOGPROBS_MAX_TOP:
+            raise ValueError(f"logprobs: an integer in [0, {LOGPROBS_MAX_TOP}] or None, got {k!r}")
+        if want == getattr(self, "_lp_next", -1):
+            return
+        err = C.create_string_buffer(1024)
+        if lib().cake_engine_set_logprobs(self._h, want, err, len(err)):
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        self._lp_next = want
+
+    def _logprobs(self, first: int, count: int) -> TokenLogprobs:
+        import numpy as np
+        k = self._lp_run
+        ids = np.empty(count, dtype=np.int32)
+        logit, lse = (np.empty(count, dtype=np.float32) for _ in range(2))
+        top_ids = np.empty((count, LOGPROBS_MAX_TOP), dtype=np.int32)
+        top_logits = np.empty((count, LOGPROBS_MAX_TOP), dtype=np.float32)
+        err = C.create_string_buffer(1024)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+        rc = lib().cake_engine_logprobs(self._h, int(first), int(count), ids.ctypes.data_as(ip),
+                                        logit.ctypes.data_as(fp), lse.ctypes.data_as(fp),
+                                        top_ids.ctypes.data_as(ip), top_logits.ctypes.data_as(fp),
+                                        err, len(err))
+        if rc:
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        top_ids = np.ascontiguousarray(top_ids[:, :k])
+        top_logits = np.ascontiguousarray(top_logits[:, :k])
+        return TokenLogprobs(ids, logit, lse, _logprob(logit, lse), top_ids, top_logits,
+                             _logprob(top_logits, lse[:, None]))
+
+    def token_logprob(self, i: int) -> TokenLogprobs:
+        """Inside ``on_token``: the record of token ``i`` of the running generate / continue
+        call (any token reported so far, the current one included), as one-row arrays."""
+        if getattr(self, "_lp_run", -1) < 0:
+            raise RuntimeError("token_logprob: the generation runs without logprobs")
+        return self._logprobs(int(i), 1)
+
     def continue_(self, max_new: int, *, eos_ids: list[int] | None = None,
                   on_token: Callable[[int], bool | None] | None = None) -> GenResult:
-        """Up to max_new more tokens after the last generate / continue (same sampling;
-        the rate counts every token: all are decode steps)."""
+        """Up to max_new more tokens after the last generate / continue (same sampling and
+        log-prob setting; the rate counts every token: all are decode steps)."""
         return self._run(lambda eos_arr, n_eos, cb, out, stats, err: lib().cake_engine_continue(
             self._h, int(max_new), eos_arr, n_eos, cb, None, out, max(1, max_new), stats, err,
-            len(err)), max_new, eos_ids, on_token)
+            len(err)), max_new, eos_ids, on_token, continued=True)
 
-    def _run(self, call, max_new, eos_ids, on_token) -> GenResult:
+    def _run(self, call, max_new, eos_ids, on_token, continued: bool = False) -> GenResult:
+        if not continued:  # a continuation keeps the setting of its generation
+            self._lp_run = getattr(self, "_lp_next", -1)
         eos = list(eos_ids or [])
         eos_arr = (C.c_int32 * max(1, len(eos)))(*eos)
         out = (C.c_int32 * max(1, max_new))()
@@ -435,9 +524,12 @@ class NativeLlama:
             raise errors[0]
         if rc:
             raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
-        return GenResult([int(out[i]) for i in range(stats.n_generated)], stats.n_prompt,
-                         stats.prefill_s, stats.decode_s, stats.tokens_per_s, stats.p50_ms,
-                         stats.p99_ms)
+        res = GenResult([int(out[i]) for i in range(stats.n_generated)], stats.n_prompt,
+                        stats.prefill_s, stats.decode_s, stats.tokens_per_s, stats.p50_ms,
+                        stats.p99_ms)
+        if getattr(self, "_lp_run", -1) >= 0:
+            res.logprobs = self._logprobs(0, stats.n_generated)
+        return res
 
 
 def owners_from_topology(topology, num_layers: int, world: int) -> list[int]:

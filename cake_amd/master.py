@@ -47,8 +47,15 @@ class Master:
             def out(s: str) -> None:
                 sys.stdout.write(s)
                 sys.stdout.flush()
+            lp_path = getattr(a, "logprobs_file", None)
+            if lp_path:  # cli.logprobs_file_refusal let only the native engine through
+                self.llm.set_logprobs(int(getattr(a, "top_logprobs", None) or 0))
             self.generate_text(out)
             sys.stdout.write("\n")
+            if lp_path:
+                from .engine import logprob_json_lines
+                Path(lp_path).write_text(
+                    "".join(logprob_json_lines(self.llm.last_result.logprobs)))
         else:
             from .models.sd.args import ImageGenerationArgs
             Path("images").mkdir(exist_ok=True)
@@ -66,18 +73,23 @@ class Master:
         if self.llm is not None:
             self.llm.reset()
 
-    def generate_text(self, stream: Callable[[str], None], max_tokens: int | None = None) -> dict:
+    def generate_text(self, stream: Callable[[str], None], max_tokens: int | None = None,
+                      on_token: Callable | None = None) -> dict:
+        """``on_token``: receives every non-EOS ``Token`` (its log-probs, when the generator
+        records them), alongside the text sink."""
         n = max_tokens if max_tokens is not None else self.ctx.args.sample_len
         llm = self.llm
         t_start = time.perf_counter()
         times: list[float] = []
 
-        def on_token(tok) -> None:
+        def emit(tok) -> None:
             times.append(time.perf_counter())
             if not tok.is_end_of_stream:
                 stream(str(tok))
+                if on_token is not None:
+                    on_token(tok)
 
-        llm.stream(n, on_token)
+        llm.stream(n, emit)
         generated = llm.generated_tokens()
         stats = {"generated": generated}
         if times:

@@ -17,6 +17,10 @@ class Token:
     id: int
     text: str | None
     is_end_of_stream: bool
+    # log-probs (generators that support set_logprobs, when asked): log p(id), and the most
+    # likely alternatives as (id, logprob) pairs in descending order
+    logprob: float | None = None
+    top_logprobs: list[tuple[int, float]] | None = None
 
     def __str__(self) -> str:
         return self.text or ""

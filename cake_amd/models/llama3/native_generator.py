@@ -35,6 +35,7 @@ class NativeLLM(TextGenerator):
         self.generated = 0
         self.last_stats = None
         self.last_result = None
+        self.logprobs: int | None = None   # set_logprobs
 
     # ------------------------------------------------------------------ factory
     @classmethod
@@ -77,6 +78,13 @@ class NativeLLM(TextGenerator):
         """Per-request sampling (API): every generate call carries it to the engine."""
         self.sampling = sampling
 
+    def set_logprobs(self, k: int | None) -> None:
+        """Log-probs of the generated tokens from the next generation on: None = off, K in
+        [0, 20] = on with the K most likely alternatives (``Token.logprob`` /
+        ``Token.top_logprobs``).  Refused by a tensor-parallel engine."""
+        self.eng.set_logprobs(k)
+        self.logprobs = None if k is None else int(k)
+
     def latency_ms(self) -> tuple[float, float] | None:
         """(p50, p99) device time per decode token of the last generation."""
         r = self.last_result
@@ -92,12 +100,18 @@ class NativeLLM(TextGenerator):
                 "engine_tokens_per_s": round(r.tokens_per_s, 3),
                 **({"walk": self.eng.walk()} if self.eng.world > 1 else {})}
 
-    def _token(self, tid: int) -> Token:
+    def _token(self, tid: int, lp=None) -> Token:
+        """lp: the token's one-row TokenLogprobs, when the generation records them."""
         try:
             text = self.tokenizer.decode([tid], skip_special_tokens=False)
         except Exception:  # noqa: BLE001  (reference logs and returns None)
             text = None
-        return Token(id=tid, text=text, is_end_of_stream=tid in self.eos_ids)
+        t = Token(id=tid, text=text, is_end_of_stream=tid in self.eos_ids)
+        if lp is not None:
+            t.logprob = float(lp.logprob[0])
+            t.top_logprobs = [(int(i), float(v)) for i, v in
+                              zip(lp.top_ids[0], lp.top_logprobs[0]) if i >= 0]
+        return t
 
     def _kw(self) -> dict:
         s = self.sampling
@@ -114,13 +128,14 @@ class NativeLLM(TextGenerator):
         later one is one more decode step of the same generation."""
         if self.generated == 0:
             self.tokens = self._prompt()
-            r = self.eng.generate(self.tokens, 1, eos_ids=[], **self._kw())
+            r = self.eng.generate(self.tokens, 1, eos_ids=[], logprobs=self.logprobs,
+                                  **self._kw())
         else:
             r = self.eng.continue_(1, eos_ids=[])
         tid = r.tokens[0]
         self.tokens.append(tid)
         self.generated += 1
-        return self._token(tid)
+        return self._token(tid, r.logprobs)
 
     def stream(self, max_tokens: int, on_token: Callable[[Token], None],
                stop_at_eos: bool = True) -> list[Token]:
@@ -135,14 +150,15 @@ class NativeLLM(TextGenerator):
             raise RuntimeError("prompt does not fit the KV cache (--max-seq-len)")
 
         def cb(tid: int) -> None:
-            t = self._token(tid)
+            lp = self.eng.token_logprob(len(out)) if self.logprobs is not None else None
+            t = self._token(tid, lp)
             out.append(t)
             self.tokens.append(tid)
             self.generated += 1
             on_token(t)
         self.last_result = self.eng.generate(
             self.tokens, min(max_tokens, room), eos_ids=sorted(self.eos_ids) if stop_at_eos else [],
-            on_token=cb, **self._kw())
+            on_token=cb, logprobs=self.logprobs, **self._kw())
         return out
 
 

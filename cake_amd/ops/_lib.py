@@ -199,3 +199,9 @@ _SIGS.update({
     "cake_lse_rows": [P, C.c_longlong, I, I, I, I, P, P, P, P, P, P],
     "cake_lse_finish": [P, P, P, I, P, P, P, P],
 })
+# log-probs of a generated token: lse + top-k of one decode row, one record (logprob.hip)
+_SIGS.update({
+    "cake_logprob_topk": [P, I, P, P, I, P, I, P, P, I, P],
+    "cake_logprob_ws_bytes": [I],
+})
+_RESTYPE["cake_logprob_ws_bytes"] = C.c_longlong

@@ -36,6 +36,8 @@ class LoopSpec(C.Structure):
         ("stream", C.c_void_p),
         ("out_tokens", C.POINTER(C.c_int32)), ("out_ms", C.POINTER(C.c_float)),
         ("out_cap", C.c_int32),
+        # per-token device records read back with the tokens (rec_bytes 0: none)
+        ("rec", C.c_void_p), ("rec_bytes", C.c_int32), ("out_rec", C.c_void_p),
     ]
 
 
@@ -134,7 +136,7 @@ def run(gs: GraphSet, *, k: int, n: int, pos: int, hist: torch.Tensor | None = N
                     C.c_void_p(hist.data_ptr() if hist is not None else None), int(base),
                     int(pos), int(n), int(chunk), eos_arr, len(eos), tok_cb, None, ann_cb, None,
                     C.c_void_p(torch.cuda.current_stream().cuda_stream), toks, ms,
-                    max(cap, n))
+                    max(cap, n), None, 0, None)
     res = LoopResult()
     rc = _lib().cake_graph_decode(C.byref(spec), C.byref(res))
     if errors:

@@ -1521,3 +1521,35 @@ def lse_finish(run_max, run_sum, key, lse, top, topv):
     _req(topv, "topv", dtype=torch.float32, shape=(T,))
     check(kernels().cake_lse_finish(_p(run_max), _p(run_sum), _p(key), T, _p(lse), _p(top),
                                     _p(topv), _stream()), "lse_finish")
+
+
+LOGPROB_REC_WORDS = 48  # int32 words of one record (192 bytes)
+
+
+def logprob_ws_bytes(V: int) -> int:
+    """Bytes of the partials workspace of :func:`logprob_topk` for a row of V logits."""
+    return int(kernels().cake_logprob_ws_bytes(int(V)))
+
+
+def logprob_topk(logits, tok, hist_len, k: int, rec, ws, ticket, max_blocks: int = 0):
+    """One log-prob record for the token `tok` (int32[1]) chosen from `logits` (f32 [V], any
+    4-byte aligned view): rec (int32 [max_rec, 48]) row `hist_len[0] - 1` <- token id, logit
+    bits, lse bits (f32), k, 20 top ids, 20 top logit bits, 4 zero words; a row index outside
+    the array writes nothing.  ws: int64, >= logprob_ws_bytes(V) bytes; ticket: int32[1],
+    zeroed once (every launch leaves it zero).  max_blocks 0: the default grid."""
+    if logits.dim() != 1 or logits.dtype != torch.float32 or not logits.is_cuda or (
+            logits.numel() > 1 and logits.stride(0) != 1):
+        raise ValueError("logprob_topk: logits must be a device float32 [V] view of unit stride")
+    V = logits.numel()
+    _req(tok, "tok", dtype=torch.int32, numel=1)
+    _req(hist_len, "hist_len", dtype=torch.int32, numel=1)
+    _req(rec, "rec", dtype=torch.int32)
+    if rec.dim() != 2 or rec.shape[1] != LOGPROB_REC_WORDS:
+        raise ValueError(f"rec: expected shape [max_rec, {LOGPROB_REC_WORDS}]")
+    _req(ws, "ws", dtype=torch.int64)
+    _req(ticket, "ticket", dtype=torch.int32, numel=1)
+    if V >= 1 and ws.numel() * 8 < logprob_ws_bytes(V):
+        raise ValueError(f"ws: expected >= {logprob_ws_bytes(V)} bytes")
+    check(kernels().cake_logprob_topk(_p(logits), V, _p(tok), _p(hist_len), int(k), _p(rec),
+                                      rec.shape[0], _p(ws), _p(ticket), int(max_blocks),
+                                      _stream()), "logprob_topk")

@@ -178,3 +178,47 @@ def quant_kv_fp8(x: torch.Tensor) -> torch.Tensor:
 def dequant_kv_fp8(codes: torch.Tensor) -> torch.Tensor:
     """f32 = fp8(code); every value is exact in bf16 and in f16."""
     return codes.view(torch.float8_e4m3fn).float()
+
+
+LOGPROB_MAX_TOP = 20
+LOGPROB_REC_WORDS = 48  # int32 words of one device record (192 bytes)
+
+
+def logprob_topk_ref(x_f32: torch.Tensor, tok: int, k: int) -> dict:
+    """Oracle of the generated-token log-prob record (logprob.hip) for one row.
+
+    ``x_f32`` is the f32 row that token selection sees: the logits after the repeat penalty,
+    before temperature, top-k / top-p and the draw.  Returns
+
+    * ``logit`` = ``x[tok]`` (float32, bit for bit), ``lse`` = ``log sum_v exp(x[v])`` in
+      float64 (``-inf`` if every logit is ``-inf``), ``logprob`` = ``float64(logit) - lse``
+      (``-inf`` when the logit is ``-inf``);
+    * ``top_ids`` (int32 [k]) / ``top_logits`` (float32 [k]): the ``k`` largest logits in
+      descending order, the lower id first at ties (a stable sort by ``(-x, id)``); entries
+      past ``min(k, V)`` are id ``-1``, logit ``-inf``; ``top_logprobs`` float64 likewise.
+
+    NaN logits are outside the contract."""
+    if not 0 <= k <= LOGPROB_MAX_TOP:
+        raise ValueError(f"k must be in [0, {LOGPROB_MAX_TOP}], got {k}")
+    x = x_f32.detach().reshape(-1).to(torch.float32).cpu()
+    V = x.numel()
+    x64 = x.double()
+    m = x64.max()
+    if torch.isinf(m) and m < 0:
+        lse = float("-inf")
+    else:
+        lse = float(m + torch.log(torch.exp(x64 - m).sum()))
+    # descending stable sort of x: equal values keep their id order
+    order = torch.sort(x, descending=True, stable=True).indices[:min(k, V)]
+    top_ids = torch.full((k,), -1, dtype=torch.int32)
+    top_logits = torch.full((k,), float("-inf"), dtype=torch.float32)
+    top_ids[:order.numel()] = order.to(torch.int32)
+    top_logits[:order.numel()] = x[order]
+
+    def lp(v: torch.Tensor) -> torch.Tensor:
+        v64 = v.double()
+        return torch.where(torch.isinf(v64) & (v64 < 0), v64, v64 - lse)
+
+    logit = x[int(tok)].clone()
+    return {"id": int(tok), "logit": logit, "lse": lse, "logprob": float(lp(logit)),
+            "top_ids": top_ids, "top_logits": top_logits, "top_logprobs": lp(top_logits)}
