@@ -80,7 +80,8 @@ def _compile_hip(src: Path, force: bool) -> Path:
 def _compile_cpp(src: Path, force: bool, extra: list[str] | None = None) -> Path:
     out = BUILD / "runtime" / (src.stem + ".o")
     out.parent.mkdir(parents=True, exist_ok=True)
-    headers = sorted((CSRC / "runtime").glob("*.h")) + [CSRC / "engine" / "llama_engine.h"]
+    headers = sorted((CSRC / "runtime").glob("*.h")) + [
+        *sorted((CSRC / "engine").glob("*.h")), CSRC / "kernels" / "cake_kernels.h"]
     if force or _newer(src, headers, out):
         _run([CXX, "-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
               "-fvisibility=hidden", *(extra or []), "-c", str(src), "-o", str(out)])
@@ -175,7 +176,7 @@ def build_engine(force: bool = False) -> Path:
     rt = CSRC / "runtime"
     objs = [_compile_cpp(rt / f"{n}.cpp", force) for n in ("json", "safetensors", "net", "proto")]
     deps = [*sorted((CSRC / "engine").glob("*.h")), *sorted(rt.glob("*.h")),
-            CSRC / "driver" / "graph_loop.h"]
+            CSRC / "driver" / "graph_loop.h", CSRC / "kernels" / "cake_kernels.h"]
     eng_objs = []
     for src in sorted((CSRC / "engine").glob("*.cpp")):  # llama_engine, sd_engine
         out = BUILD / "engine" / (src.stem + ".o")

@@ -22,7 +22,7 @@
 #include <mutex>
 #include <tuple>
 
-#define CAKE_API extern "C" __attribute__((visibility("default")))
+#include "../kernels/cake_kernels.h"
 
 namespace {
 

@@ -28,8 +28,6 @@
 #include <cstring>
 #include <vector>
 
-#define CAKE_API extern "C" __attribute__((visibility("default")))
-
 #include "graph_loop.h"
 
 namespace {

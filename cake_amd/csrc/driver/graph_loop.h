@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../kernels/cake_kernels.h"  // CAKE_API
+
 extern "C" {
 typedef int32_t (*cake_token_cb)(void* ctx, int32_t token);
 typedef int32_t (*cake_announce_cb)(void* ctx, int32_t first, int32_t count);

@@ -42,165 +42,12 @@
 #include <vector>
 
 #include "../driver/graph_loop.h"
+#include "../kernels/cake_kernels.h"
 #include "../runtime/json.h"
 #include "../runtime/net.h"
 #include "../runtime/proto.h"
 #include "../runtime/safetensors.h"
 #include "engine_util.h"
-
-#define CAKE_API extern "C" __attribute__((visibility("default")))
-
-// gfx950 kernel entry points (libcake_kernels.so)
-extern "C" {
-int cake_cast16(int src_kind, int dt, const void* src, void* dst, size_t n, hipStream_t st);
-int cake_fill_normal(int dt, void* dst, size_t n, float mean, float std, unsigned long long key,
-                     hipStream_t st);
-int cake_embed(int dt, const void* table, const int* tok, int T, int H, float* out, hipStream_t st);
-int cake_rmsnorm(int dt, const float* x, const void* w, float eps, int T, int H, void* out,
-                 hipStream_t st);
-int cake_flash_attn(int dt, const void* q, const void* k, const void* v, void* o, int B, int H,
-                    int Hkv, int N, int M, int D, const long long* strides, float scale,
-                    int causal, int pos0, hipStream_t st);
-long long cake_gemm_ws_floats(int cfg, int splits, int M, int N, int K, int gated);
-int cake_gemm(int dt, int epi, int cfg, int splits, const void* a, long long lda, const void* b,
-              long long ldb, void* c, long long ldc, const void* bias, void* resid,
-              long long ldr, float* ws, const void* zeros, int M, int N, int K, hipStream_t st);
-int cake_blaslt_gemm(int dt, int out, const void* a, long long lda, const void* w, long long ldw,
-                     void* c, long long ldc, int M, int N, int K, void* ws, size_t ws_bytes,
-                     hipStream_t st);
-int cake_silu_mul_rows(int dt, const void* gu, size_t T, int I, void* out, hipStream_t st);
-int cake_attn_decode(int dt, const float* q, const void* kc, const void* vc, const int* pos,
-                     int S, int nh, int nkv, int hd, float scale, float* part,
-                     unsigned int* tickets, void* out, hipStream_t st);
-int cake_attn_set_split_cap(int cap);
-int cake_attn_set_heads(int max_keys, int waves);
-int cake_attn_set_head_prefetch(int pfd);
-int cake_attn_decode_heads(int dt, const float* q, const void* kc, const void* vc, const int* pos,
-                           int S, int nh, int nkv, int hd, float scale, void* out, hipStream_t st);
-int cake_attn_splits(int Tk);
-int cake_attn_max_split(int S);
-int cake_gemv_x16(int dt, const void* x, const void* w, int K, int N, float* out, int accumulate,
-                  hipStream_t st);
-int cake_swiglu(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
-                const void* wu, int K, int I, void* act, hipStream_t st);
-// FP8 e4m3fn weight-only projections (quant_fp8.hip, gemv_w8*.hip)
-int cake_quant_rows_fp8(int dt, const void* w16, int N, int K, void* w8, float* scale,
-                        hipStream_t st);
-int cake_dequant_rows_fp8(int dt, const void* w8, const float* scale, int N, int K, void* out16,
-                          hipStream_t st);
-int cake_swiglu_w8(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
-                   const void* wu, const float* sg, const float* su, int K, int I, void* act,
-                   hipStream_t st);
-int cake_gemv_x16_w8(int dt, const void* x, const void* w, const float* scale, int K, int N,
-                     float* out, int accumulate, hipStream_t st);
-// FP8 x FP8 MFMA GEMM of the quantised prefill (gemm_w8a8.hip): e4m3 activation codes with one
-// f32 scale per token against the resident projection codes; cfg < 0 = its planner's tile
-int cake_gemm_w8a8(int dt, int epi, int cfg, const void* a8, long long lda, const float* sa,
-                   const void* w8, long long ldb, const float* sw, void* c, long long ldc,
-                   float* r32, long long ldr, int M, int N, int K, hipStream_t st);
-// sequence scoring (score.hip): streaming log-sum-exp / target gather / argmax over one
-// vocabulary chunk of f32 logits, per-row state carried from chunk to chunk
-int cake_lse_rows(const float* logits, long long ld, int T, int Vc, int v0, int first,
-                  const int32_t* target, float* run_max, double* run_sum, float* tgt,
-                  unsigned long long* key, hipStream_t st);
-int cake_lse_finish(const float* run_max, const double* run_sum, const unsigned long long* key,
-                    int T, float* lse, int32_t* top, float* topv, hipStream_t st);
-// log-probs of a generated token (logprob.hip): one 192-byte record at rec[*hist_len - 1]
-int cake_logprob_topk(const float* logits, int V, const int32_t* tok, const int32_t* hist_len,
-                      int K, void* rec, int max_rec, void* ws, unsigned int* ticket,
-                      int max_blocks, hipStream_t st);
-long long cake_logprob_ws_bytes(int V);
-// MXFP4 weight-only projections (quant_mxfp4.hip, gemv_w4*.hip)
-int cake_quant_rows_mxfp4(int dt, const void* w16, int N, int K, void* w4, void* e8,
-                          hipStream_t st);
-int cake_dequant_rows_mxfp4(int dt, const void* w4, const void* e8, int N, int K, void* out16,
-                            hipStream_t st);
-int cake_swiglu_w4(int dt, const float* resid, const void* norm_w, float eps, const void* wg,
-                   const void* wu, const void* eg, const void* eu, int K, int I, void* act,
-                   hipStream_t st);
-int cake_gemv_x16_w4(int dt, const void* x, const void* w, const void* e8, int K, int N,
-                     float* out, int accumulate, hipStream_t st);
-// The KV writers with the cache's format as their last argument (CakeEngineOpts.kv_fmt; 0 =
-// the 16-bit entry points cake_qkv_rope* / cake_rope_kv), the prefill read and the decode
-// attention of the FP8 e4m3 KV cache
-int cake_qkv_rope_kvf(int dt, const float* resid, const void* norm_w, float eps, const void* wq,
-                      const void* wk, const void* wv, int K, int nh, int nkv, int hd,
-                      const float* inv_freq, const int* pos, float* q_out, void* kcache,
-                      void* vcache, int S, hipStream_t st, int kv_fmt);
-int cake_qkv_rope_w8_kvf(int dt, const float* resid, const void* norm_w, float eps,
-                         const void* wq, const void* wk, const void* wv, const float* sq,
-                         const float* sk, const float* sv, int K, int nh, int nkv, int hd,
-                         const float* inv_freq, const int* pos, float* q_out, void* kcache,
-                         void* vcache, int S, hipStream_t st, int kv_fmt);
-int cake_qkv_rope_w4_kvf(int dt, const float* resid, const void* norm_w, float eps,
-                         const void* wq, const void* wk, const void* wv, const void* eq,
-                         const void* ek, const void* ev, int K, int nh, int nkv, int hd,
-                         const float* inv_freq, const int* pos, float* q_out, void* kcache,
-                         void* vcache, int S, hipStream_t st, int kv_fmt);
-int cake_rope_kv_kvf(int dt, void* q, const void* k, const void* v, int ldq, int ld, int T, int nh,
-                     int nkv, int hd, const float* inv_freq, int pos0, int S, void* kc, void* vc,
-                     hipStream_t st, int kv_fmt);
-int cake_dequant_kv_fp8(int dt, const void* k8, const void* v8, int nkv, int S, int hd, int Tk,
-                        void* k16, void* v16, hipStream_t st);
-int cake_attn_decode_kv8(int dt, const float* q, const void* kc8, const void* vc8, const int* pos,
-                         int S, int nh, int nkv, int hd, float scale, float* part,
-                         unsigned int* tickets, void* out, hipStream_t st);
-int cake_gemv_norm_f32(int dt, const float* resid, const void* norm_w, float eps, const void* w,
-                       int K, int N, float* out, hipStream_t st);
-int cake_head_select(int dt, const float* resid, const void* norm_w, float eps, const void* w,
-                     int K, int N, float* out, int* hist, int* hist_len, int last_n,
-                     float penalty, unsigned long long* slot, unsigned int* ticket, int* tok,
-                     int* pos, int max_hist, const void* embed, float* emb_out, hipStream_t st);
-// quantised lm_head (gemv_w8_head.hip, gemv_w4_head.hip)
-int cake_gemv_norm_f32_w8(int dt, const float* resid, const void* norm_w, float eps,
-                          const void* w8, const float* scale, int K, int N, float* out,
-                          hipStream_t st);
-int cake_head_select_w8(int dt, const float* resid, const void* norm_w, float eps, const void* w8,
-                        const float* scale, int K, int N, float* out, int* hist, int* hist_len,
-                        int last_n, float penalty, unsigned long long* slot, unsigned int* ticket,
-                        int* tok, int* pos, int max_hist, const void* embed, float* emb_out,
-                        hipStream_t st);
-int cake_gemv_norm_f32_w4(int dt, const float* resid, const void* norm_w, float eps,
-                          const void* w4, const void* e8, int K, int N, float* out,
-                          hipStream_t st);
-int cake_head_select_w4(int dt, const float* resid, const void* norm_w, float eps, const void* w4,
-                        const void* e8, int K, int N, float* out, int* hist, int* hist_len,
-                        int last_n, float penalty, unsigned long long* slot, unsigned int* ticket,
-                        int* tok, int* pos, int max_hist, const void* embed, float* emb_out,
-                        hipStream_t st);
-int cake_repeat_penalty(float* logits, const int* hist, const int* hist_len, int last_n,
-                        float penalty, hipStream_t st);
-int cake_argmax(const float* logits, int V, unsigned long long* slot, hipStream_t st);
-int cake_sample_threshold(const float* logits, int V, float temperature, int top_k, float top_p,
-                          unsigned int* thr, hipStream_t st);
-int cake_gumbel_argmax(const float* logits, int V, float temperature, unsigned long long seed,
-                       const int* step, const unsigned int* thr, unsigned long long* slot,
-                       hipStream_t st);
-int cake_finalize_token(unsigned long long* slot, int* tok, int* hist, int* hist_len, int* pos,
-                        int max_hist, hipStream_t st);
-int cake_hop_alloc(size_t bytes, void** ptr);
-int cake_sum_slices(float* out, const float* src, int W, long long stride, long long n,
-                    int accumulate, hipStream_t st);
-long long cake_ar_inbox_words(int world, int n);
-int cake_ar_sum(const float* partial, float* out, int n, int accumulate, void* const* peers,
-                const void* inbox, unsigned int* seq, int* err, int rank, int world,
-                double timeout_s, hipStream_t st);
-int cake_ar_max_key(unsigned long long* slot, void* const* peers, const void* inbox,
-                    unsigned int* seq, int* err, int rank, int world, double timeout_s,
-                    hipStream_t st);
-int cake_ar_gather(const float* shard, int off, int n_local, float* full, int n,
-                   void* const* peers, const void* inbox, unsigned int* seq, int* err, int rank,
-                   int world, double timeout_s, hipStream_t st);
-int cake_select_shard(float* logits, int V, int off, const int* hist, const int* hist_len,
-                      int last_n, float penalty, float temperature, unsigned long long seed,
-                      unsigned long long* slot, hipStream_t st);
-int cake_hop_free(void* ptr);
-int cake_hop_words(int H, int nhdr, int bf16);
-int cake_hop_send(const float* src, int H, int nhdr, int bf16, void* dst_inbox, unsigned int* seq,
-                  hipStream_t st);
-int cake_hop_recv(const void* inbox, int H, int nhdr, int bf16, float* dst, unsigned int* seq,
-                  int* err, double timeout_s, hipStream_t st);
-}
 
 namespace cake {
 namespace {
@@ -209,12 +56,10 @@ namespace {
 // (the one that holds cake_attn_decode) when it was built with CAKE_BUILD_EXPERIMENTAL=1;
 // all null otherwise.
 struct AoFns {
-  int (*supported)(int, int, int, int) = nullptr;
-  long long (*ws_floats)(int, int) = nullptr;
-  long long (*ticket_words)(int, int) = nullptr;
-  int (*run)(int, const float*, const void*, const void*, const int*, int, int, int, int, float,
-             const void*, int, int, float*, int, float*, unsigned int*, unsigned int*,
-             hipStream_t) = nullptr;
+  decltype(&cake_attn_oproj_supported) supported = nullptr;
+  decltype(&cake_attn_oproj_ws_floats) ws_floats = nullptr;
+  decltype(&cake_attn_oproj_ticket_words) ticket_words = nullptr;
+  decltype(&cake_attn_oproj) run = nullptr;
 };
 
 AoFns ao_fns() {
@@ -231,9 +76,6 @@ AoFns ao_fns() {
   if (!f.supported || !f.ws_floats || !f.ticket_words || !f.run) f = AoFns{};
   return f;
 }
-
-constexpr int kHeadSelectMaxLastN = 256;  // gemv.hip head_select window bound
-constexpr int kAttnMaxSplit = 64;         // attention.hip kMaxSplit
 
 
 // ---------------------------------------------------------------------------
@@ -306,8 +148,6 @@ struct Cfg {
   }
 };
 
-
-constexpr int kEpiStore = 0, kEpiResid32 = 1, kEpiSwiglu = 3, kEpiStore32 = 6;
 
 // Contiguous layer shards, rank 0 lighter by the head's weight in blocks
 // (parallel/pipeline.py shard_layers + head_cost_in_layers).
@@ -402,11 +242,11 @@ class Llama {
     if (hfmt_ != 0 && hfmt_ != 1 && hfmt_ != 2)
       throw Error("head_fmt must be 0 (model dtype), 1 (fp8 e4m3 lm_head) or 2 (mxfp4 lm_head)");
     if (hfmt_ != 0 && tp) throw Error(kNoQHeadTP);
-    if (kvfmt_ != 0 && kvfmt_ != 1 && kvfmt_ != 2)
+    if (kvfmt_ != kKv16 && kvfmt_ != kKvFp8 && kvfmt_ != kKvFp8Emu)
       throw Error("kv_fmt must be 0 (model dtype), 1 (fp8 e4m3 KV cache) or 2 (fp8 values in a "
                   "16-bit cache: the test oracle)");
-    if (kvfmt_ != 0 && tp) throw Error(kNoKvTP);
-    if (kvfmt_ != 0) {
+    if (kvfmt_ != kKv16 && tp) throw Error(kNoKvTP);
+    if (kvfmt_ != kKv16) {
       // the fp8 cache has core 2's split launch only: none of the experimental decode
       // paths (docs/ENV.md) reads it
       for (const char* name : {"CAKE_ATTN_OPROJ", "CAKE_ATTN_HEADS", "CAKE_MK", "CAKE_QKV_ATTN"}) {
@@ -452,7 +292,7 @@ class Llama {
     S_ = o.max_seq > 0 ? o.max_seq : 4096;
     k_ = std::max(1, o.steps_per_graph);
     if (cfg_.H % 8 || cfg_.hd % 2 || cfg_.nh % cfg_.nkv) throw Error("unsupported model shape");
-    if (kvfmt_ != 0 && cfg_.hd != 64 && cfg_.hd != 128)
+    if (kvfmt_ != kKv16 && cfg_.hd != 64 && cfg_.hd != 128)
       throw Error("an fp8 KV cache needs a head dimension of 64 or 128");
     // this rank's compute shapes: the whole model, or its tensor-parallel slice
     lc_ = cfg_;
@@ -541,10 +381,10 @@ class Llama {
                               : (dt_ == 0 ? "bf16" : "f16"),
                  !head_ ? "none" : hfmt_ == 1 ? "fp8 e4m3" : hfmt_ == 2 ? "mxfp4"
                                                 : (dt_ == 0 ? "bf16" : "f16"),
-                 kvfmt_ == 1 ? "fp8 e4m3"
-                 : kvfmt_ == 2 ? (dt_ == 0 ? "fp8 e4m3 values in bf16 (test oracle)"
-                                           : "fp8 e4m3 values in f16 (test oracle)")
-                               : (dt_ == 0 ? "bf16" : "f16"),
+                 kvfmt_ == kKvFp8 ? "fp8 e4m3"
+                 : kvfmt_ == kKvFp8Emu ? (dt_ == 0 ? "fp8 e4m3 values in bf16 (test oracle)"
+                                                   : "fp8 e4m3 values in f16 (test oracle)")
+                                       : (dt_ == 0 ? "bf16" : "f16"),
                  pfmt_ == 1 ? ", prefill fp8 e4m3 activations" : "",
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
@@ -698,8 +538,8 @@ class Llama {
   // the partials workspace and the ticket are allocated at the first call that turns it on.
   void set_logprobs(int top_k) {
     hip_check(hipSetDevice(dev_), "hipSetDevice");
-    if (top_k > kLpMaxTop)
-      throw Error("log-probs: at most " + std::to_string(kLpMaxTop) +
+    if (top_k > kLpMaxK)
+      throw Error("log-probs: at most " + std::to_string(kLpMaxK) +
                   " alternatives per token, got " + std::to_string(top_k));
     if (top_k >= 0 && tp_ > 1)
       throw Error("log-probs are not available on a tensor-parallel engine (the vocabulary is "
@@ -734,8 +574,8 @@ class Llama {
       ids[i] = (int32_t)r[0];
       std::memcpy(logit + i, r + 1, 4);
       std::memcpy(lse + i, r + 2, 4);
-      std::memcpy(top_ids + (size_t)i * kLpMaxTop, r + 4, 4 * kLpMaxTop);
-      std::memcpy(top_logits + (size_t)i * kLpMaxTop, r + 4 + kLpMaxTop, 4 * kLpMaxTop);
+      std::memcpy(top_ids + (size_t)i * kLpMaxK, r + 4, 4 * kLpMaxK);
+      std::memcpy(top_logits + (size_t)i * kLpMaxK, r + 4 + kLpMaxK, 4 * kLpMaxK);
     }
   }
 
@@ -1156,7 +996,6 @@ class Llama {
   uint16_t* sc_head_ = nullptr;
   // log-probs of generated tokens (set_logprobs): device records indexed like hist_, the
   // kernel's partials and ticket; the host copy holds the last call's records in token order
-  static constexpr int kLpMaxTop = 20, kLpRecWords = 48;
   int lp_k_ = -1;       // the next generate()'s setting
   bool lp_on_ = false;  // the last generate() / continue() call recorded
   int lp_n_ = 0;        // its records readable so far
@@ -1440,7 +1279,7 @@ class Llama {
   void alloc_state() {
     const Cfg& c = lc_;
     kv_session(0);  // session 0: generation / pipeline
-    if (kvfmt_ == 1) {  // prefill's 16-bit view of one layer's live prefix
+    if (kvfmt_ == kKvFp8) {  // prefill's 16-bit view of one layer's live prefix
       const size_t n = (size_t)c.nkv * S_ * c.hd;
       kv16_k_ = dalloc<uint16_t>(n);
       kv16_v_ = dalloc<uint16_t>(n);
@@ -1456,7 +1295,7 @@ class Llama {
     resid_ = dalloc<float>(c.H + 4);
     hidden_ = dalloc<float>((size_t)S_ * c.H);  // prefill hidden (peer-written in a pipeline)
     q_ = dalloc<float>(nq);
-    part_ = dalloc<float>(2 * (size_t)c.nh * kAttnMaxSplit * (c.hd + 2));
+    part_ = dalloc<float>(2 * (size_t)c.nh * kMaxSplit * (c.hd + 2));
     logits_ = dalloc<float>(c.V);
     attn_out_ = dalloc<uint16_t>(nq);
     act_ = dalloc<uint16_t>(c.I);
@@ -1472,7 +1311,7 @@ class Llama {
     scratch_resid_ = dalloc<float>(c.H + 4);  // + the hop header (self-tests)
     zeros_ = dalloc<int32_t>(64);
     hip_check(hipMemset(tickets_, 0, sizeof(unsigned int) * (2 * c.nkv + 2)), "memset");
-    hip_check(hipMemset(part_, 0, sizeof(float) * 2 * c.nh * kAttnMaxSplit * (c.hd + 2)), "memset");
+    hip_check(hipMemset(part_, 0, sizeof(float) * 2 * c.nh * kMaxSplit * (c.hd + 2)), "memset");
     hip_check(hipMemset(sel_ticket_, 0, sizeof(unsigned int)), "memset");
     hip_check(hipMemset(slot_, 0, sizeof(unsigned long long)), "memset");
     hip_check(hipMemset(zeros_, 0, sizeof(int32_t) * 64), "memset");
@@ -1483,11 +1322,11 @@ class Llama {
     {
       const char* e = std::getenv("CAKE_ATTN_OPROJ");
       // (reads o_proj as 16-bit rows: off with fp8 and mxfp4 weights)
-      if (e && std::string(e) == "1" && wfmt_ == 0 && kvfmt_ == 0) ao_ = ao_fns();
+      if (e && std::string(e) == "1" && wfmt_ == 0 && kvfmt_ == kKv16) ao_ = ao_fns();
       ao_ok_ = ao_.run != nullptr && ao_.supported(c.nh, c.nkv, c.hd, c.H) != 0;
     }
     // CAKE_ATTN_HEADS=<max keys>[:<waves>]: the head-parallel short-context attention
-    if (!ao_ok_ && kvfmt_ == 0) {
+    if (!ao_ok_ && kvfmt_ == kKv16) {
       const char* e = std::getenv("CAKE_ATTN_HEADS");
       int mx = 0, nw = 2, pfd = 2;
       if (e && *e) std::sscanf(e, "%d:%d:%d", &mx, &nw, &pfd);
@@ -1517,7 +1356,7 @@ class Llama {
     hip_check(hipDeviceSynchronize(), "sync");  // null-stream memsets before st_ work
   }
 
-  size_t kv_esize() const { return kvfmt_ == 1 ? 1 : 2; }  // bytes per cache element
+  size_t kv_esize() const { return kvfmt_ == kKvFp8 ? 1 : 2; }  // bytes per cache element
   size_t kv_elems() const { return owned_.size() * (size_t)lc_.nkv * S_ * lc_.hd; }  // of K
   void* kc(int l) const { return cur_.k + (size_t)l * lc_.nkv * S_ * lc_.hd * kv_esize(); }
   void* vc(int l) const { return cur_.v + (size_t)l * lc_.nkv * S_ * lc_.hd * kv_esize(); }
@@ -1831,7 +1670,7 @@ class Llama {
       k_check(cake_rope_kv_kvf(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
                                inv_freq_, pos0, S_, kc(l), vc(l), st_, kvfmt_), "rope_kv");
       const void *kr = kc(l), *vr = vc(l);  // what the attention reads
-      if (kvfmt_ == 1) {
+      if (kvfmt_ == kKvFp8) {
         // the live prefix, the rows just written included, widened into the 16-bit scratch:
         // one extra pass over it per layer per prefill call (stream order keeps the layers'
         // uses of the scratch apart)
@@ -2003,7 +1842,7 @@ class Llama {
   // head-parallel for a short context, split over the context otherwise
   void attn(int l) {
     const Cfg& c = lc_;
-    if (kvfmt_ == 1)
+    if (kvfmt_ == kKvFp8)
       k_check(cake_attn_decode_kv8(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
                                    part_, tickets_, attn_out_, st_), "attn_decode_kv8");
     else if (short_step_)
@@ -2055,7 +1894,8 @@ class Llama {
       k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
                                 wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
                                 pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
-      if (kvfmt_ != 1 && short_step_ && ao_ok_) {  // one split: attention + o_proj in one launch
+      // one split: attention + o_proj in one launch
+      if (kvfmt_ != kKvFp8 && short_step_ && ao_ok_) {
         k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.wo,
                                 nq, c.H, tp_ > 1 ? partial_ : resid_, tp_ > 1 ? 0 : 1, ao_ws_,
                                 ao_tickets_, tickets_ + 2 * c.nkv, st_), "attn_oproj");

@@ -42,59 +42,7 @@
 #include "../runtime/safetensors.h"
 #include "engine_util.h"
 
-#define CAKE_API extern "C" __attribute__((visibility("default")))
-
-// gfx950 kernel entry points (libcake_kernels.so)
-extern "C" {
-int cake_cast16(int src_kind, int dt, const void* src, void* dst, size_t n, hipStream_t st);
-int cake_fill_normal(int dt, void* dst, size_t n, float mean, float std, unsigned long long key,
-                     hipStream_t st);
-long long cake_gemm_ws_floats(int cfg, int splits, int M, int N, int K, int gated);
-int cake_gemm(int dt, int epi, int cfg, int splits, const void* a, long long lda, const void* b,
-              long long ldb, void* c, long long ldc, const void* bias, void* resid,
-              long long ldr, float* ws, const void* zeros, int M, int N, int K, hipStream_t st);
-int cake_flash_attn_ws(int dt, const void* q, const void* k, const void* v, void* o, int B, int H,
-                       int Hkv, int N, int M, int D, const long long* strides, float scale,
-                       int causal, int pos0, void* ws, long long ws_bytes, hipStream_t st);
-int cake_attn512(int dt, const void* q, const void* k, const void* v, void* o, int B, int N, int M,
-                 long long sq, long long sk, long long sv, long long so, long long bq,
-                 long long bk, long long bv, long long bo, float scale, const void* zeros,
-                 hipStream_t st);
-int cake_groupnorm_nhwc2(int dt, const void* x, const void* x2, int Cx, void* cat,
-                         const void* gamma, const void* beta, int N, int HW, int C, int G,
-                         float eps, int silu_act, double* part, unsigned int* tickets,
-                         float* stats, void* y, hipStream_t st);
-int cake_groupnorm_nhwc_splits(int HW);
-int cake_layernorm(int dt, const void* x, const void* gamma, const void* beta, long long rows,
-                   int C, float eps, void* y, hipStream_t st);
-int cake_conv2d_nhwc2(int dt, const void* x, const void* w, const void* bias, const float* bias2,
-                      const void* resid, void* out, float* ws, const void* zeros, int N, int H,
-                      int W, int IC, int OC, int KH, int KW, int stride, int pad, int up, int cfg,
-                      int splits, int th, int tw, int bias2_ld, int layout, hipStream_t st);
-int cake_conv1x1_small(int dt, const void* x, const void* w, const void* bias, void* out, int N,
-                       int HW, int IC, int OC, int layout, hipStream_t st);
-int cake_timestep_embed(int dt, const float* t_table, const int* step, int B, int dim, int flip,
-                        float shift, int out16, void* out, hipStream_t st);
-int cake_sched_step(int dt, float* x, const void* pred, long long n, int cfg, float guidance,
-                    const void* coef, const int* step, const void* seed, void* next_in,
-                    hipStream_t st);
-int cake_step_advance(int* step, hipStream_t st);
-int cake_scale_copy(int dt, const float* x, long long n, float scale, int dup, void* out,
-                    hipStream_t st);
-int cake_to_rgb8(int dt, const void* img, int B, int H, int W, int nhwc, void* out,
-                 hipStream_t st);
-int cake_clip_embed(int dt, const void* tok, const void* pos, const int* ids, int rows, int T,
-                    int D, int V, void* out, hipStream_t st);
-int cake_widen16(int dt, const void* x, long long n, float* y, hipStream_t st);
-int cake_hop_alloc(size_t bytes, void** ptr);
-int cake_hop_free(void* ptr);
-int cake_bulk_send(const void* const* srcs, const unsigned long long* bytes,
-                   const unsigned long long* offs, int nseg, void* dst_rx,
-                   unsigned long long rx_bytes, unsigned int* seq, unsigned int* count,
-                   hipStream_t st);
-int cake_bulk_recv(const void* rx, unsigned long long bytes, void* dst, unsigned int* seq,
-                   int* err, double timeout_s, hipStream_t st);
-}
+#include "../kernels/cake_kernels.h"
 
 namespace cake {
 namespace {
@@ -382,8 +330,6 @@ const char* kPartNames[] = {"unet", "vae", "clip", "clip2"};
 
 const char* kEpiNames[] = {"store", "resid32", "add16", "swiglu", "geglu", "partial", "store32",
                            "silu", "quick_gelu", "gelu"};
-enum Epi { kStore = 0, kResid32 = 1, kAdd16 = 2, kGeglu = 4, kStore32 = 6, kSilu = 7,
-           kQuickGelu = 8, kGelu = 9 };
 
 // packed convolution weight: [OC][KH][KW][IC] (16-bit), bias [OC] (OC padded to 4 for the
 // VAE's RGB output; the 1x1 few-channel form keeps [OC][IC])
@@ -1459,13 +1405,13 @@ class SdEngine {
   void gemm(int epi, const uint16_t* x, long long lda, int M, int K, const uint16_t* w, int Nv,
             const uint16_t* bias, void* out, long long ldc, const void* resid = nullptr,
             long long ldr = 0) {
-    const bool gated = epi == 3 || epi == kGeglu;
+    const bool gated = epi == kEpiSwiglu || epi == kEpiGeglu;
     const int N = gated ? Nv / 2 : Nv;
     const auto pl = planner_.plan_mfma(M, Nv, K, kEpiNames[epi]);  // no library path here
     float* ws = pl.second > 1
                     ? gemm_ws((size_t)cake_gemm_ws_floats(pl.first, pl.second, M, N, K, gated ? 1 : 0))
                     : nullptr;
-    const bool f32out = epi == kResid32 || epi == kStore32;
+    const bool f32out = epi == kEpiResid32 || epi == kEpiStore32;
     k_check(cake_gemm(dt_, epi, pl.first, pl.second, x, lda, w, K, f32out ? nullptr : out,
                       f32out ? 0 : ldc,
                       bias, f32out ? out : const_cast<void*>(resid), f32out ? ldc : ldr, ws,
@@ -1706,35 +1652,35 @@ class SdEngine {
     uint16_t* h = group_norm(A, x.p, nullptr, C, B_, T, C, t.nw, t.nb, cfg_.unet.groups, 1e-6f,
                              false);
     uint16_t* hp = new16(A, (size_t)rows * C);
-    gemm(kStore, h, C, (int)rows, C, t.pin_w, C, t.pin_b, hp, C);
+    gemm(kEpiStore, h, C, (int)rows, C, t.pin_w, C, t.pin_b, hp, C);
     h = hp;
     for (const auto& blk : t.blocks) {
       // self-attention: one q|k|v GEMM, flash attention, o-proj + residual
       uint16_t* n1 = layer_norm(A, h, rows, C, blk.n1w, blk.n1b, 1e-5f);
       uint16_t* qkv = new16(A, (size_t)rows * 3 * C);
-      gemm(kStore, n1, C, (int)rows, C, blk.qkv, 3 * C, nullptr, qkv, 3 * C);
+      gemm(kEpiStore, n1, C, (int)rows, C, blk.qkv, 3 * C, nullptr, qkv, 3 * C);
       uint16_t* a = attention(A, qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, B_, T, T,
                               t.heads, C, false);
       uint16_t* x1 = new16(A, (size_t)rows * C);
-      gemm(kAdd16, a, C, (int)rows, C, blk.o1w, C, blk.o1b, x1, C, h, C);
+      gemm(kEpiAdd16, a, C, (int)rows, C, blk.o1w, C, blk.o1b, x1, C, h, C);
       // cross-attention on the cached context k|v
       uint16_t* n2 = layer_norm(A, x1, rows, C, blk.n2w, blk.n2b, 1e-5f);
       uint16_t* q = new16(A, (size_t)rows * C);
-      gemm(kStore, n2, C, (int)rows, C, blk.q2, C, nullptr, q, C);
+      gemm(kEpiStore, n2, C, (int)rows, C, blk.q2, C, nullptr, q, C);
       uint16_t* a2 = attention(A, q, C, blk.kv_cache, 2 * C, blk.kv_cache + C, 2 * C, B_, T, kTok,
                                t.heads, C, false);
       uint16_t* x2 = new16(A, (size_t)rows * C);
-      gemm(kAdd16, a2, C, (int)rows, C, blk.o2w, C, blk.o2b, x2, C, x1, C);
+      gemm(kEpiAdd16, a2, C, (int)rows, C, blk.o2w, C, blk.o2b, x2, C, x1, C);
       // GEGLU feed-forward, residual in the output projection
       uint16_t* n3 = layer_norm(A, x2, rows, C, blk.n3w, blk.n3b, 1e-5f);
       uint16_t* ff = new16(A, (size_t)rows * 4 * C);
-      gemm(kGeglu, n3, C, (int)rows, C, blk.ffi_w, 8 * C, blk.ffi_b, ff, 4 * C);
+      gemm(kEpiGeglu, n3, C, (int)rows, C, blk.ffi_w, 8 * C, blk.ffi_b, ff, 4 * C);
       uint16_t* x3 = new16(A, (size_t)rows * C);
-      gemm(kAdd16, ff, 4 * C, (int)rows, 4 * C, blk.ffo_w, C, blk.ffo_b, x3, C, x2, C);
+      gemm(kEpiAdd16, ff, 4 * C, (int)rows, 4 * C, blk.ffo_w, C, blk.ffo_b, x3, C, x2, C);
       h = x3;
     }
     uint16_t* y = new16(A, (size_t)rows * C);
-    gemm(kAdd16, h, C, (int)rows, C, t.pout_w, C, t.pout_b, y, C, x.p, C);
+    gemm(kEpiAdd16, h, C, (int)rows, C, t.pout_w, C, t.pout_b, y, C, x.p, C);
     return {y, x.H, x.W, C};
   }
 
@@ -1743,7 +1689,8 @@ class SdEngine {
     const int ctx = cfg_.unet.ctx;
     auto run = [&](TransformerW& t) {
       for (auto& blk : t.blocks)
-        gemm(kStore, ctx_, ctx, B * kTok, ctx, blk.kv2, 2 * t.ch, nullptr, blk.kv_cache, 2 * t.ch);
+        gemm(kEpiStore, ctx_, ctx, B * kTok, ctx, blk.kv2, 2 * t.ch, nullptr, blk.kv_cache,
+             2 * t.ch);
     };
     for (auto& d : down_)
       for (auto& t : d.att) run(t);
@@ -1801,11 +1748,11 @@ class SdEngine {
     k_check(cake_timestep_embed(dt_, ttab, tidx, B, C0, u.flip ? 1 : 0, (float)u.shift, 1, emb, st_),
             "timestep_embed");
     uint16_t* e1 = new16(A, (size_t)B * temb_dim_);
-    gemm(kSilu, emb, C0, B, C0, t1w_, temb_dim_, t1b_, e1, temb_dim_);
+    gemm(kEpiSilu, emb, C0, B, C0, t1w_, temb_dim_, t1b_, e1, temb_dim_);
     uint16_t* e2 = new16(A, (size_t)B * temb_dim_);
-    gemm(kSilu, e1, temb_dim_, B, temb_dim_, t2w_, temb_dim_, t2b_, e2, temb_dim_);
+    gemm(kEpiSilu, e1, temb_dim_, B, temb_dim_, t2w_, temb_dim_, t2b_, e2, temb_dim_);
     float* tb = new32(A, (size_t)B * temb_cols_);
-    gemm(kStore32, e2, temb_dim_, B, temb_dim_, tall_w_, temb_cols_, tall_b_, tb, temb_cols_);
+    gemm(kEpiStore32, e2, temb_dim_, B, temb_dim_, tall_w_, temb_cols_, tall_b_, tb, temb_cols_);
     return {tb, B > 1 ? temb_cols_ : 0};
   }
 
@@ -2342,16 +2289,16 @@ class SdEngine {
     for (const auto& l : cw.layers) {
       uint16_t* h = layer_norm(A, x, T, D, l.ln1w, l.ln1b, (float)c.eps);
       uint16_t* qkv = new16(A, (size_t)T * 3 * D);
-      gemm(kStore, h, D, T, D, l.qkv, 3 * D, l.qkv_b, qkv, 3 * D);
+      gemm(kEpiStore, h, D, T, D, l.qkv, 3 * D, l.qkv_b, qkv, 3 * D);
       uint16_t* a = attention(A, qkv, 3 * D, qkv + D, 3 * D, qkv + 2 * D, 3 * D, 1, T, T, c.heads,
                               D, true);
       uint16_t* x1 = new16(A, (size_t)T * D);
-      gemm(kAdd16, a, D, T, D, l.ow, D, l.ob, x1, D, x, D);
+      gemm(kEpiAdd16, a, D, T, D, l.ow, D, l.ob, x1, D, x, D);
       h = layer_norm(A, x1, T, D, l.ln2w, l.ln2b, (float)c.eps);
       uint16_t* m = new16(A, (size_t)T * c.I);
-      gemm(c.quick_gelu ? kQuickGelu : kGelu, h, D, T, D, l.f1w, c.I, l.f1b, m, c.I);
+      gemm(c.quick_gelu ? kEpiQuickGelu : kEpiGelu, h, D, T, D, l.f1w, c.I, l.f1b, m, c.I);
       uint16_t* x2 = new16(A, (size_t)T * D);
-      gemm(kAdd16, m, c.I, T, c.I, l.f2w, D, l.f2b, x2, D, x1, D);
+      gemm(kEpiAdd16, m, c.I, T, c.I, l.f2w, D, l.f2b, x2, D, x1, D);
       x = x2;
     }
     return layer_norm(A, x, T, D, cw.fw, cw.fb, (float)c.eps);
@@ -2413,11 +2360,11 @@ class SdEngine {
     uint16_t* hn = group_norm(A, x.p, nullptr, C, 1, T, C, at.nw, at.nb, cfg_.vae.groups, 1e-6f,
                               false);
     uint16_t* qkv = new16(A, (size_t)T * 3 * C);
-    gemm(kStore, hn, C, T, C, at.qkv, 3 * C, at.qkv_b, qkv, 3 * C);
+    gemm(kEpiStore, hn, C, T, C, at.qkv, 3 * C, at.qkv_b, qkv, 3 * C);
     uint16_t* a = attention(A, qkv, 3 * C, qkv + C, 3 * C, qkv + 2 * C, 3 * C, 1, T, T, 1, C,
                             false);
     uint16_t* y = new16(A, (size_t)T * C);
-    gemm(kAdd16, a, C, T, C, at.ow, C, at.ob, y, C, x.p, C);
+    gemm(kEpiAdd16, a, C, T, C, at.ow, C, at.ob, y, C, x.p, C);
     return {y, x.H, x.W, C};
   }
 

@@ -33,7 +33,7 @@
 namespace cake {
 
 constexpr int kChunk = 64;        // keys per LDS chunk (one per lane)
-constexpr int kMaxSplit = 64;     // splits per kv head (partials merged lane-parallel)
+// kMaxSplit (cake_kernels.h): splits per kv head (partials merged lane-parallel)
 
 template <int NREP> struct AttnGeom {
   static constexpr int NW = NREP < 4 ? 4 : NREP;  // waves (>= 4 so loads stay wide)

@@ -13,11 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define CAKE_API extern "C" __attribute__((visibility("default")))
+#include "cake_kernels.h"  // CAKE_API, every entry point's declaration, DType / KvFmt
 
 namespace cake {
-
-enum DType : int { kBF16 = 0, kF16 = 1, kF32 = 2 };
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) {
   return __uint_as_float(((uint32_t)h) << 16);
@@ -64,10 +62,7 @@ __device__ __forceinline__ void unpack8(const uint4 v, float* o) {
   }
 }
 
-// ---- FP8 KV cache (CakeEngineOpts.kv_fmt; oracle: ops/reference.py quant_kv_fp8)
-// kv_fmt 0: 16-bit cache; 1: one OCP e4m3fn code per element, no scale; 2: the code's
-// value kept in a 16-bit cache (exact in bf16 and f16: the test oracle of format 1).
-enum KvFmt : int { kKv16 = 0, kKvFp8 = 1, kKvFp8Emu = 2 };
+// ---- FP8 KV cache (KvFmt: cake_kernels.h)
 
 // two f32 -> two e4m3fn codes (bits 0-7: a, 8-15: b): one v_cvt_pk_fp8_f32 (RNE) after an
 // explicit clamp to +-448, so a finite input never gives the NaN code whatever the

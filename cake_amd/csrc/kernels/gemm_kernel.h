@@ -12,17 +12,7 @@ namespace cake {
 
 constexpr int kGBK = 64;  // k per step (128-byte rows)
 
-enum GemmEpi : int {
-  kEpiStore = 0,   // C16 = acc (+ bias)
-  kEpiResid32 = 1, // R32 += acc (+ bias)
-  kEpiAdd16 = 2,   // C16 = acc (+ bias) + R16
-  kEpiSwiglu = 3,  // C16[:, f] = silu(acc_gate) * acc_up
-  kEpiGeglu = 4,   // C16[:, f] = acc_h * gelu_tanh(acc_gate)
-  kEpiPartial = 5, // W32[split] = acc (split-K slab, virtual column order)
-  kEpiStore32 = 6, // R32 = acc (+ bias)              (f32 output, e.g. conv time biases)
-  kEpiSilu = 7,    // C16 = act(acc (+ bias)), act = GemmArgs::act: SiLU (time-embedding
-                   // MLP), quick_gelu / erf-GELU (CLIP MLP); host ids 7 / 8 / 9
-};
+// (GemmEpi, the epilogue ids: cake_kernels.h)
 
 // the activation of kEpiSilu (runtime-uniform: one kernel instance for all three)
 __device__ __forceinline__ float gemm_act(int act, float x) {

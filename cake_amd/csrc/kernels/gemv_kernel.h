@@ -787,8 +787,8 @@ static int launch_head_select(int dt, const float* resid, const void* norm_w, fl
                               int* hist_len, int last_n, float penalty, unsigned long long* slot,
                               unsigned int* ticket, int* tok, int* pos, int max_hist,
                               const void* embed, float* emb_out, hipStream_t st) {
-  if (last_n < 0 || last_n > 256 || !(penalty > 0.f) || slot == nullptr || ticket == nullptr ||
-      (embed != nullptr && emb_out == nullptr))
+  if (last_n < 0 || last_n > kHeadSelectMaxLastN || !(penalty > 0.f) || slot == nullptr ||
+      ticket == nullptr || (embed != nullptr && emb_out == nullptr))
     return (int)hipErrorInvalidValue;
   const HeadSel hs{hist, hist_len, last_n, penalty, slot, ticket, tok, hist, hist_len, pos,
                    max_hist, (const uint16_t*)embed, emb_out, K};

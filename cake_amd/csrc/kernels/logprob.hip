@@ -42,9 +42,8 @@ constexpr int kLpNV = 2;                                // 16-byte loads per thr
 constexpr int kLpPiece = kLpThreads * kLpNV * 4;        // 2048 columns
 constexpr int kLpKeys = kLpNV * 4 + 1;                  // + this thread's scalar column
 constexpr int kLpMaxBlocks = 64;                        // one wave merges the partials
-constexpr int kLpMaxK = 20;
 constexpr int kLpSlot = 24;                             // u64 words per partial: S, max, 20 keys
-constexpr int kLpRecWords = 48;
+// kLpMaxK = 20, kLpRecWords = 48: cake_kernels.h
 
 // keys of piece columns [0, n) at src (vocabulary id g0 + column); empty slots are 0, which
 // is below every real key.  Columns [0, lead) and [lead + 4 nvec, n) are read one by one, the

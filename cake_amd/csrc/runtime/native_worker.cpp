@@ -82,18 +82,13 @@ int run_native_worker(const NativeWorkerOpts& o, const TopoNode& node) {
     std::fprintf(stderr, "%s: %s\n", tag.c_str(), dlerror());
     return 1;
   }
-  using OpenLayers = void* (*)(const char*, const CakeEngineOpts*, const int32_t*, int32_t, char*,
-                               int32_t);
-  using Forward = int32_t (*)(void*, uint64_t, const int32_t*, int32_t, int32_t, float*, int32_t,
-                              char*, int32_t);
-  using Drop = void (*)(void*, uint64_t);
-  using InfoFn = int32_t (*)(void*, int32_t*);
-  using CloseFn = void (*)(void*);
-  auto open_layers = reinterpret_cast<OpenLayers>(dlsym(h, "cake_engine_open_layers"));
-  auto forward = reinterpret_cast<Forward>(dlsym(h, "cake_engine_forward"));
-  auto drop = reinterpret_cast<Drop>(dlsym(h, "cake_engine_drop_session"));
-  auto einfo = reinterpret_cast<InfoFn>(dlsym(h, "cake_engine_info"));
-  auto eclose = reinterpret_cast<CloseFn>(dlsym(h, "cake_engine_close"));
+  auto open_layers =
+      reinterpret_cast<decltype(&cake_engine_open_layers)>(dlsym(h, "cake_engine_open_layers"));
+  auto forward = reinterpret_cast<decltype(&cake_engine_forward)>(dlsym(h, "cake_engine_forward"));
+  auto drop =
+      reinterpret_cast<decltype(&cake_engine_drop_session)>(dlsym(h, "cake_engine_drop_session"));
+  auto einfo = reinterpret_cast<decltype(&cake_engine_info)>(dlsym(h, "cake_engine_info"));
+  auto eclose = reinterpret_cast<decltype(&cake_engine_close)>(dlsym(h, "cake_engine_close"));
   if (!open_layers || !forward || !drop || !einfo || !eclose) {
     std::fprintf(stderr, "%s: engine symbols missing in %s\n", tag.c_str(), lib.c_str());
     return 1;
@@ -313,19 +308,13 @@ int run_native_sd_worker(const NativeWorkerOpts& o, const TopoNode& node) {
     std::fprintf(stderr, "%s: %s\n", tag.c_str(), dlerror());
     return 1;
   }
-  using Open = void* (*)(const char*, const CakeSdOpts*, char*, int32_t);
-  using Text = int32_t (*)(void*, int32_t, const int32_t*, int32_t, float*, char*, int32_t);
-  using Unet = int32_t (*)(void*, const float*, int32_t, float, const float*, float*, char*, int32_t);
-  using Vae = int32_t (*)(void*, const float*, float*, char*, int32_t);
-  using Info = void (*)(void*, int32_t*);
-  using Close = void (*)(void*);
-  auto vae_enc = reinterpret_cast<Vae>(dlsym(h, "cake_sd_vae_encode"));
-  auto open = reinterpret_cast<Open>(dlsym(h, "cake_sd_open"));
-  auto text = reinterpret_cast<Text>(dlsym(h, "cake_sd_text"));
-  auto unet = reinterpret_cast<Unet>(dlsym(h, "cake_sd_unet"));
-  auto vae = reinterpret_cast<Vae>(dlsym(h, "cake_sd_vae_decode"));
-  auto info = reinterpret_cast<Info>(dlsym(h, "cake_sd_info"));
-  auto sclose = reinterpret_cast<Close>(dlsym(h, "cake_sd_close"));
+  auto vae_enc = reinterpret_cast<decltype(&cake_sd_vae_encode)>(dlsym(h, "cake_sd_vae_encode"));
+  auto open = reinterpret_cast<decltype(&cake_sd_open)>(dlsym(h, "cake_sd_open"));
+  auto text = reinterpret_cast<decltype(&cake_sd_text)>(dlsym(h, "cake_sd_text"));
+  auto unet = reinterpret_cast<decltype(&cake_sd_unet)>(dlsym(h, "cake_sd_unet"));
+  auto vae = reinterpret_cast<decltype(&cake_sd_vae_decode)>(dlsym(h, "cake_sd_vae_decode"));
+  auto info = reinterpret_cast<decltype(&cake_sd_info)>(dlsym(h, "cake_sd_info"));
+  auto sclose = reinterpret_cast<decltype(&cake_sd_close)>(dlsym(h, "cake_sd_close"));
   if (!open || !text || !unet || !vae || !vae_enc || !info || !sclose) {
     std::fprintf(stderr, "%s: SD engine symbols missing in %s\n", tag.c_str(), lib.c_str());
     return 1;

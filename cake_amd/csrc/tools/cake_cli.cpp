@@ -182,20 +182,16 @@ bool in_choices(const std::string& v, const char* choices) {
 // then the reference's rate line (master.rs:93-121) on stderr.
 // ---------------------------------------------------------------------------
 struct EngineApi {
-  void* (*open)(const char*, const CakeEngineOpts*, char*, int32_t);
-  void* (*open_pp)(const char*, const CakeEngineOpts*, const CakePipeOpts*, char*, int32_t);
-  void* (*open_tp)(const char*, const CakeEngineOpts*, const CakeTPOpts*, char*, int32_t);
-  void* (*open_remote)(const char*, const CakeEngineOpts*, const CakeRemoteOpts*, char*, int32_t);
-  int32_t (*serve)(void*, char*, int32_t);
-  int32_t (*generate)(void*, const int32_t*, int32_t, int32_t, const CakeEngineSampling*,
-                      const int32_t*, int32_t, cake_engine_token_cb, void*, int32_t*, int32_t,
-                      CakeEngineStats*, char*, int32_t);
-  int32_t (*score)(void*, const int32_t*, int32_t, int32_t, float*, float*, int32_t*, float*,
-                   char*, int32_t);
-  int32_t (*set_logprobs)(void*, int32_t, char*, int32_t);
-  int32_t (*logprobs)(void*, int32_t, int32_t, int32_t*, float*, float*, int32_t*, float*, char*,
-                      int32_t);
-  void (*close)(void*);
+  decltype(&cake_engine_open) open;
+  decltype(&cake_engine_open_pp) open_pp;
+  decltype(&cake_engine_open_tp) open_tp;
+  decltype(&cake_engine_open_remote) open_remote;
+  decltype(&cake_engine_serve) serve;
+  decltype(&cake_engine_generate) generate;
+  decltype(&cake_engine_score) score;
+  decltype(&cake_engine_set_logprobs) set_logprobs;
+  decltype(&cake_engine_logprobs) logprobs;
+  decltype(&cake_engine_close) close;
 };
 
 bool native_text_eligible(cake::PyArgs& o, bool text, bool worker, bool has_topology) {

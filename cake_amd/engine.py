@@ -69,72 +69,78 @@ PREFILL_FMT_SHIFT = 8
 _lib = None
 
 
+def _bind(L) -> None:
+    """Prototypes of llama_engine.h on a loaded library (tests/test_abi_cpu.py compares them
+    with the header)."""
+    P, I = C.c_void_p, C.c_int32
+    L.cake_engine_open.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.c_char_p, I]
+    L.cake_engine_open.restype = P
+    L.cake_engine_open_pp.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.POINTER(PipeOpts),
+                                      C.c_char_p, I]
+    L.cake_engine_open_pp.restype = P
+    L.cake_engine_open_tp.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.POINTER(TPOpts),
+                                      C.c_char_p, I]
+    L.cake_engine_open_tp.restype = P
+    L.cake_engine_open_remote.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
+                                          C.POINTER(RemoteOpts), C.c_char_p, I]
+    L.cake_engine_open_remote.restype = P
+    L.cake_engine_serve.argtypes = [P, C.c_char_p, I]
+    L.cake_engine_serve.restype = I
+    L.cake_engine_rank_info.argtypes = [P, C.POINTER(C.c_int32)]
+    L.cake_engine_rank_info.restype = I
+    L.cake_engine_info.argtypes = [P, C.POINTER(C.c_int32)]
+    L.cake_engine_info.restype = I
+    L.cake_engine_eos.argtypes = [P, C.POINTER(C.c_int32), I]
+    L.cake_engine_eos.restype = I
+    L.cake_engine_weight_bytes.argtypes = [P]
+    L.cake_engine_weight_bytes.restype = C.c_int64
+    L.cake_engine_kv_bytes.argtypes = [P]
+    L.cake_engine_kv_bytes.restype = C.c_int64
+    L.cake_engine_open_layers.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
+                                          C.POINTER(C.c_int32), I, C.c_char_p, I]
+    L.cake_engine_open_layers.restype = P
+    L.cake_engine_forward.argtypes = [P, C.c_uint64, C.POINTER(C.c_int32), I, I,
+                                      C.POINTER(C.c_float), I, C.c_char_p, I]
+    L.cake_engine_forward.restype = I
+    L.cake_engine_drop_session.argtypes = [P, C.c_uint64]
+    L.cake_engine_drop_session.restype = None
+    L.cake_engine_generate.argtypes = [P, C.POINTER(C.c_int32), I, I, C.POINTER(EngineSampling),
+                                       C.POINTER(C.c_int32), I, TOKEN_CB, P,
+                                       C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
+                                       C.c_char_p, I]
+    L.cake_engine_generate.restype = I
+    L.cake_engine_continue.argtypes = [P, I, C.POINTER(C.c_int32), I, TOKEN_CB, P,
+                                       C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
+                                       C.c_char_p, I]
+    L.cake_engine_continue.restype = I
+    L.cake_engine_forced_logits.argtypes = [P, C.POINTER(C.c_int32), I, C.POINTER(C.c_int32),
+                                            I, C.POINTER(C.c_float), C.c_char_p, I]
+    L.cake_engine_forced_logits.restype = I
+    L.cake_engine_walk.argtypes = [P, C.c_char_p, I]
+    L.cake_engine_walk.restype = I
+    L.cake_engine_prefill_logits.argtypes = [P, C.POINTER(C.c_int32), I,
+                                             C.POINTER(C.c_float), C.c_char_p, I]
+    L.cake_engine_prefill_logits.restype = I
+    FP = C.POINTER(C.c_float)
+    L.cake_engine_score.argtypes = [P, C.POINTER(C.c_int32), I, I, FP, FP,
+                                    C.POINTER(C.c_int32), FP, C.c_char_p, I]
+    L.cake_engine_score.restype = I
+    IP = C.POINTER(C.c_int32)
+    L.cake_engine_set_logprobs.argtypes = [P, I, C.c_char_p, I]
+    L.cake_engine_set_logprobs.restype = I
+    L.cake_engine_logprobs.argtypes = [P, I, I, IP, FP, FP, IP, FP, C.c_char_p, I]
+    L.cake_engine_logprobs.restype = I
+    L.cake_engine_close.argtypes = [P]
+    L.cake_engine_close.restype = None
+
+
 def lib() -> C.CDLL:
     global _lib
     if _lib is None:
         if not LIB_PATH.exists():
             raise RuntimeError(f"{LIB_PATH} missing: run `python -m cake_amd.build`")
         L = C.CDLL(str(LIB_PATH))
-        P, I = C.c_void_p, C.c_int32
-        L.cake_engine_open.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.c_char_p, I]
-        L.cake_engine_open.restype = P
-        L.cake_engine_open_pp.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.POINTER(PipeOpts),
-                                          C.c_char_p, I]
-        L.cake_engine_open_pp.restype = P
-        L.cake_engine_open_tp.argtypes = [C.c_char_p, C.POINTER(EngineOpts), C.POINTER(TPOpts),
-                                          C.c_char_p, I]
-        L.cake_engine_open_tp.restype = P
-        L.cake_engine_open_remote.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
-                                              C.POINTER(RemoteOpts), C.c_char_p, I]
-        L.cake_engine_open_remote.restype = P
-        L.cake_engine_serve.argtypes = [P, C.c_char_p, I]
-        L.cake_engine_serve.restype = I
-        L.cake_engine_rank_info.argtypes = [P, C.POINTER(C.c_int32)]
-        L.cake_engine_rank_info.restype = I
-        L.cake_engine_info.argtypes = [P, C.POINTER(C.c_int32)]
-        L.cake_engine_info.restype = I
-        L.cake_engine_eos.argtypes = [P, C.POINTER(C.c_int32), I]
-        L.cake_engine_eos.restype = I
-        L.cake_engine_weight_bytes.argtypes = [P]
-        L.cake_engine_weight_bytes.restype = C.c_int64
-        L.cake_engine_kv_bytes.argtypes = [P]
-        L.cake_engine_kv_bytes.restype = C.c_int64
-        L.cake_engine_open_layers.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
-                                              C.POINTER(C.c_int32), I, C.c_char_p, I]
-        L.cake_engine_open_layers.restype = P
-        L.cake_engine_forward.argtypes = [P, C.c_uint64, C.POINTER(C.c_int32), I, I,
-                                          C.POINTER(C.c_float), I, C.c_char_p, I]
-        L.cake_engine_forward.restype = I
-        L.cake_engine_drop_session.argtypes = [P, C.c_uint64]
-        L.cake_engine_drop_session.restype = None
-        L.cake_engine_generate.argtypes = [P, C.POINTER(C.c_int32), I, I, C.POINTER(EngineSampling),
-                                           C.POINTER(C.c_int32), I, TOKEN_CB, P,
-                                           C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
-                                           C.c_char_p, I]
-        L.cake_engine_generate.restype = I
-        L.cake_engine_continue.argtypes = [P, I, C.POINTER(C.c_int32), I, TOKEN_CB, P,
-                                           C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
-                                           C.c_char_p, I]
-        L.cake_engine_continue.restype = I
-        L.cake_engine_forced_logits.argtypes = [P, C.POINTER(C.c_int32), I, C.POINTER(C.c_int32),
-                                                I, C.POINTER(C.c_float), C.c_char_p, I]
-        L.cake_engine_forced_logits.restype = I
-        L.cake_engine_walk.argtypes = [P, C.c_char_p, I]
-        L.cake_engine_walk.restype = I
-        L.cake_engine_prefill_logits.argtypes = [P, C.POINTER(C.c_int32), I,
-                                                 C.POINTER(C.c_float), C.c_char_p, I]
-        L.cake_engine_prefill_logits.restype = I
-        FP = C.POINTER(C.c_float)
-        L.cake_engine_score.argtypes = [P, C.POINTER(C.c_int32), I, I, FP, FP,
-                                        C.POINTER(C.c_int32), FP, C.c_char_p, I]
-        L.cake_engine_score.restype = I
-        IP = C.POINTER(C.c_int32)
-        L.cake_engine_set_logprobs.argtypes = [P, I, C.c_char_p, I]
-        L.cake_engine_set_logprobs.restype = I
-        L.cake_engine_logprobs.argtypes = [P, I, I, IP, FP, FP, IP, FP, C.c_char_p, I]
-        L.cake_engine_logprobs.restype = I
-        L.cake_engine_close.argtypes = [P]
-        L.cake_engine_close.restype = None
+        _bind(L)
         _lib = L
     return _lib
 

@@ -12,11 +12,9 @@ scripts/tune_gemm.py on the GPU box).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from ._lib import check, kernels
+from ._lib import check, kernels as _lib
 
 EPI = {"store": 0, "resid32": 1, "add16": 2, "swiglu": 3, "geglu": 4, "store32": 6, "silu": 7,
        "quick_gelu": 8, "gelu": 9}
@@ -48,25 +46,9 @@ NUM_CUS = 256
 LIB = -1
 LIB_EPIS = ("store", "resid32", "store32", "swiglu")
 _LIB_WS_BYTES = 32 << 20
-_bound = False
 _plans: dict = {}
 _ws: dict = {}
 _zeros: dict = {}
-
-
-def _lib():
-    global _bound
-    lib = kernels()
-    if not _bound:
-        P, I, L = C.c_void_p, C.c_int, C.c_longlong
-        lib.cake_gemm.argtypes = [I, I, I, I, P, L, P, L, P, L, P, P, L, P, P, I, I, I, P]
-        lib.cake_gemm.restype = I
-        lib.cake_gemm_ws_floats.argtypes = [I, I, I, I, I, I]
-        lib.cake_gemm_ws_floats.restype = L
-        lib.cake_blaslt_gemm.argtypes = [I, I, P, L, P, L, P, L, I, I, I, P, C.c_size_t, P]
-        lib.cake_blaslt_gemm.restype = I
-        _bound = True
-    return lib
 
 
 def _zeros16(dev) -> torch.Tensor:
@@ -327,7 +309,7 @@ def _lib_gemm(x2, lda, w, ldb, epi, out2, ldc, r2, ldr, M, N, K) -> None:
             gu = _lib_gu[(dev, st, x2.dtype)] = torch.empty(M * 2 * N, device=dev,
                                                             dtype=x2.dtype)
         run(0, gu.data_ptr(), 2 * N, 2 * N)
-        check(kernels().cake_silu_mul_rows(dt, gu.data_ptr(), M, N, out2.data_ptr(), st),
+        check(_lib().cake_silu_mul_rows(dt, gu.data_ptr(), M, N, out2.data_ptr(), st),
               "silu_mul_rows")
 
 

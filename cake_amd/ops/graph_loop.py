@@ -18,7 +18,7 @@ from typing import Callable
 
 import torch
 
-from ._lib import check, kernels
+from ._lib import check, kernels as _lib
 
 TOKEN_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32)
 ANNOUNCE_CB = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32)
@@ -44,19 +44,6 @@ class LoopSpec(C.Structure):
 class LoopResult(C.Structure):
     _fields_ = [("n_tokens", C.c_int32), ("replays", C.c_int32), ("pos", C.c_int32),
                 ("stopped", C.c_int32), ("wall_s", C.c_double)]
-
-
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = kernels()
-    if not _bound:
-        lib.cake_graph_decode.argtypes = [C.POINTER(LoopSpec), C.POINTER(LoopResult)]
-        lib.cake_graph_decode.restype = C.c_int
-        _bound = True
-    return lib
 
 
 @dataclass

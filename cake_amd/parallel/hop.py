@@ -17,37 +17,7 @@ import os
 
 import torch
 
-from ..ops._lib import check, kernels
-
-_SIGS = {
-    "cake_hop_alloc": [C.c_size_t, C.POINTER(C.c_void_p)],
-    "cake_hop_free": [C.c_void_p],
-    "cake_ipc_handle": [C.c_void_p, C.c_void_p],
-    "cake_ipc_handle_size": [],
-    "cake_ipc_open": [C.c_void_p, C.POINTER(C.c_void_p)],
-    "cake_ipc_close": [C.c_void_p],
-    "cake_hop_words": [C.c_int, C.c_int, C.c_int],
-    "cake_hop_send": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
-    "cake_hop_recv": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.c_double, C.c_void_p],
-    "cake_bulk_send": [C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                       C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p],
-    "cake_bulk_recv": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
-                       C.c_void_p],
-}
-_bound = False
-
-
-def _lib():
-    global _bound
-    lib = kernels()
-    if not _bound:
-        for name, argtypes in _SIGS.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = C.c_int
-        _bound = True
-    return lib
+from ..ops._lib import check, kernels as _lib
 
 
 def hop_timeout_s() -> float:

@@ -64,38 +64,44 @@ class SdResult(C.Structure):
 _bound = False
 
 
+def _bind(L) -> None:
+    """Prototypes of sd_engine.h on a loaded library (tests/test_abi_cpu.py compares them with
+    the header)."""
+    P, I, F = C.c_void_p, C.c_int32, C.c_float
+    FP = C.POINTER(C.c_float)
+    L.cake_sd_open.argtypes = [C.c_char_p, C.POINTER(SdOpts), C.c_char_p, I]
+    L.cake_sd_open.restype = P
+    L.cake_sd_generate.argtypes = [P, C.POINTER(SdGenArgs), C.POINTER(C.c_uint8), FP,
+                                   C.POINTER(C.c_double), C.POINTER(SdResult), C.c_char_p, I]
+    L.cake_sd_generate.restype = I
+    L.cake_sd_close.argtypes = [P]
+    L.cake_sd_close.restype = None
+    L.cake_sd_info.argtypes = [P, C.POINTER(C.c_int32)]
+    L.cake_sd_info.restype = None
+    L.cake_sd_text.argtypes = [P, I, C.POINTER(C.c_int32), I, FP, C.c_char_p, I]
+    L.cake_sd_text.restype = I
+    L.cake_sd_unet.argtypes = [P, FP, I, F, FP, FP, C.c_char_p, I]
+    L.cake_sd_unet.restype = I
+    L.cake_sd_vae_decode.argtypes = [P, FP, FP, C.c_char_p, I]
+    L.cake_sd_vae_decode.restype = I
+    L.cake_sd_vae_encode.argtypes = [P, FP, FP, C.c_char_p, I]
+    L.cake_sd_vae_encode.restype = I
+    L.cake_sd_vae_encode_remote.argtypes = [P, FP, FP, C.c_char_p, I]
+    L.cake_sd_vae_encode_remote.restype = I
+    L.cake_sd_open_split.argtypes = [C.c_char_p, C.POINTER(SdOpts), C.POINTER(SdSplitOpts),
+                                     C.c_char_p, I]
+    L.cake_sd_open_split.restype = P
+    L.cake_sd_serve.argtypes = [P, C.c_char_p, I]
+    L.cake_sd_serve.restype = I
+    L.cake_sd_split_info.argtypes = [P, C.POINTER(C.c_int32)]
+    L.cake_sd_split_info.restype = None
+
+
 def lib() -> C.CDLL:
     global _bound
     L = _engine_lib()
     if not _bound:
-        P, I, F = C.c_void_p, C.c_int32, C.c_float
-        FP = C.POINTER(C.c_float)
-        L.cake_sd_open.argtypes = [C.c_char_p, C.POINTER(SdOpts), C.c_char_p, I]
-        L.cake_sd_open.restype = P
-        L.cake_sd_generate.argtypes = [P, C.POINTER(SdGenArgs), C.POINTER(C.c_uint8), FP,
-                                       C.POINTER(C.c_double), C.POINTER(SdResult), C.c_char_p, I]
-        L.cake_sd_generate.restype = I
-        L.cake_sd_close.argtypes = [P]
-        L.cake_sd_close.restype = None
-        L.cake_sd_info.argtypes = [P, C.POINTER(C.c_int32)]
-        L.cake_sd_info.restype = None
-        L.cake_sd_text.argtypes = [P, I, C.POINTER(C.c_int32), I, FP, C.c_char_p, I]
-        L.cake_sd_text.restype = I
-        L.cake_sd_unet.argtypes = [P, FP, I, F, FP, FP, C.c_char_p, I]
-        L.cake_sd_unet.restype = I
-        L.cake_sd_vae_decode.argtypes = [P, FP, FP, C.c_char_p, I]
-        L.cake_sd_vae_decode.restype = I
-        L.cake_sd_vae_encode.argtypes = [P, FP, FP, C.c_char_p, I]
-        L.cake_sd_vae_encode.restype = I
-        L.cake_sd_vae_encode_remote.argtypes = [P, FP, FP, C.c_char_p, I]
-        L.cake_sd_vae_encode_remote.restype = I
-        L.cake_sd_open_split.argtypes = [C.c_char_p, C.POINTER(SdOpts), C.POINTER(SdSplitOpts),
-                                         C.c_char_p, I]
-        L.cake_sd_open_split.restype = P
-        L.cake_sd_serve.argtypes = [P, C.c_char_p, I]
-        L.cake_sd_serve.restype = I
-        L.cake_sd_split_info.argtypes = [P, C.POINTER(C.c_int32)]
-        L.cake_sd_split_info.restype = None
+        _bind(L)
         _bound = True
     return L
 

@@ -33,8 +33,6 @@ def main():
     big = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
     stamps = torch.zeros(nkv * 64 * 8, dtype=torch.int64, device=dev)
     lib = kernels()
-    lib.cake_attn_set_stamps.argtypes = [C.c_void_p]
-    lib.cake_attn_set_stamps.restype = C.c_int
     impls = [int(x) for x in os.environ.get("IMPLS", "1,2").split(",")]
     minks = [int(x) for x in os.environ.get("MINKS", "64").split(",")]
     targets = [int(x) for x in os.environ.get("TARGETS", "16").split(",")]

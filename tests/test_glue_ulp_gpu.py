@@ -1,7 +1,6 @@
 """RoPE + KV-cache write, the decode QKV epilogue at the last Llama-3.1 position, SiLU * up,
 the residual add, the embedding gather, the 16-bit casts and the RGB8 store: against float64
 under the rule of tests/_ulp.py, or bit for bit where the operation is exact."""
-import ctypes
 
 import pytest
 import torch
@@ -247,9 +246,6 @@ SRC = [torch.bfloat16, torch.float16, torch.float32]
 def _cast16(src, dst_kind, cuda):
     from cake_amd.ops._lib import kernels
     fn = kernels().cake_cast16
-    fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                   ctypes.c_void_p]
-    fn.restype = ctypes.c_int
     s = src.to(cuda)
     out = torch.full((src.numel() + 16,), SENTINEL, dtype=torch.int16, device=cuda)
     rc = fn(SRC.index(src.dtype), dst_kind, s.data_ptr(), out.data_ptr(), src.numel(),
