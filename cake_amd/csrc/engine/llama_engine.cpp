@@ -223,6 +223,15 @@ Json msg(const char* cmd) {
   return j;
 }
 
+// the decode GEMV kinds that read a packed (13-bit) copy of their bf16 weights by default:
+// those whose in-graph kernel time, at the best tuning found, fell below the 16-bit twin's by
+// more than the run-to-run spread in the 8B decode graph: gate | up, down_proj and the
+// lm_head; q | k | v and o_proj were not faster at any tuning tried.  The
+// figures of every kind, adopted or not, are in profiles/pack13_decode_tuning_sweep.jsonl and
+// profiles/pack13_decode8b_kernel_table.txt; a kind that is not adopted gets no copy.
+// CAKE_PACK16_KINDS overrides (qkv, o, gu, down, head).
+static const char* const kPack13Kinds = "gu,down,head";
+
 // ---------------------------------------------------------------------------
 // the engine
 // ---------------------------------------------------------------------------
@@ -389,6 +398,7 @@ class Llama {
                  (long long)weight_bytes_, rank(), (int)owned_.size());
     alloc_state();
     warm_library();
+    pack13_all();  // after the KV cache and the workspaces: it takes what HBM they left
     {
       size_t fr = 0, tot = 0;
       (void)hipMemGetInfo(&fr, &tot);
@@ -446,6 +456,7 @@ class Llama {
   const Cfg& cfg() const { return cfg_; }
   int max_seq() const { return S_; }
   int64_t weight_bytes() const { return weight_bytes_; }
+  int64_t packed_bytes() const { return packed_bytes_; }
   int64_t kv_bytes() const { return 2 * (int64_t)kv_elems() * kv_esize(); }
 
   void prefill_logits(const int32_t* prompt, int T, float* host_logits) {
@@ -842,6 +853,14 @@ class Llama {
   }
 
  private:
+  struct P13Mat {  // one matrix packed by cake_pack13_rows: one allocation, three parts
+    uint8_t* planes = nullptr;
+    int* hdr = nullptr;
+    uint16_t* raw = nullptr;  // null: no raw rows
+    // the sub-matrix from row r0 on (q | k | v, gate | up: packed as one matrix)
+    const uint8_t* p(size_t r0, size_t K) const { return planes + r0 * (K / 8 * 13); }
+    const int* h(size_t r0) const { return hdr + r0; }
+  };
   // weight_fmt 1: wqkv / wo / wgu / wd hold e4m3 codes, s* their f32 row scales (packed as
   // the rows are: q|k|v, gate|up).  weight_fmt 2: they hold packed e2m1 codes [N, K/2], e*
   // their e8m0 block-scale bytes [N, K/32] (packed the same way).
@@ -849,7 +868,15 @@ class Llama {
     void *ln1, *wqkv, *wo, *ln2, *wgu, *wd;
     float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
     uint8_t *eqkv = nullptr, *eo = nullptr, *egu = nullptr, *ed = nullptr;
+    P13Mat pqkv, po, pgu, pd;  // the packed twins decode reads (pack13_all); planes null: none
   };
+  // CAKE_PACK16 (docs/ENV.md): the lossless 13-bit copies of the bf16 projections and lm_head
+  // (kernels/gemv_p13_kernel.h) the decode GEMVs stream instead of the 16-bit rows, which
+  // stay resident for prefill, the f16 path, tensor parallelism and the oracles
+  P13Mat phead_;
+  int64_t packed_bytes_ = 0;
+  int packed_mats_ = 0, packed_raw_rows_ = 0;
+  bool pack_full_ = false;  // the HBM reserve was reached: the matrices after it stay 16-bit
   struct Mode {
     bool fused = true;  // greedy with the fused head_select tail
     bool greedy = true;
@@ -1354,6 +1381,79 @@ class Llama {
       hip_check(hipMemset(ar_err_, 0, sizeof(int) * 4), "memset");
     }
     hip_check(hipDeviceSynchronize(), "sync");  // null-stream memsets before st_ work
+  }
+
+  // One matrix [N, K] of 16-bit rows -> its packed twin, if K is whole tiles and the copy
+  // fits above the HBM reserve (`required`: not fitting is an error).  kind: the row pairing
+  // of the GEMV that reads it (cake::PackKind: 0 adjacent rows, 1 head halves, 2 gate | up).
+  void pack13_one(int kind, const void* rows16, size_t N, size_t K, int hd, bool required,
+                  P13Mat& out) {
+    constexpr size_t kReserve = (size_t)4 << 30;  // left free for sessions and library workspaces
+    if (pack_full_ || K % 2048 != 0) return;
+    const int nraw = cake_pack13_rows(kind, rows16, (int)N, (int)K, hd, nullptr, nullptr, nullptr,
+                                      0, st_);
+    k_check(nraw < 0 ? -nraw : 0, "pack13_rows (count)");
+    const size_t planes = N * (K / 8 * 13), hdrs = (N * 4 + 15) / 16 * 16;
+    const size_t bytes = (size_t)cake_pack13_bytes((int)N, (int)K, nraw);
+    size_t fr = 0, tot = 0;
+    hip_check(hipMemGetInfo(&fr, &tot), "hipMemGetInfo");
+    if (fr < bytes + kReserve) {
+      if (required)
+        throw Error("CAKE_PACK16=1: the packed copy of a [" + std::to_string(N) + ", " +
+                    std::to_string(K) + "] matrix (" + std::to_string(bytes >> 20) +
+                    " MiB) does not fit above the 4 GiB reserve (" + std::to_string(fr >> 20) +
+                    " MiB free)");
+      pack_full_ = true;
+      return;
+    }
+    uint8_t* blk = dalloc<uint8_t>(bytes);
+    P13Mat m;
+    m.planes = blk;
+    m.hdr = reinterpret_cast<int*>(blk + planes);
+    m.raw = nraw ? reinterpret_cast<uint16_t*>(blk + planes + hdrs) : nullptr;
+    const int got = cake_pack13_rows(kind, rows16, (int)N, (int)K, hd, m.planes, m.hdr, m.raw,
+                                     nraw, st_);
+    k_check(got < 0 ? -got : (got == nraw ? 0 : (int)hipErrorUnknown), "pack13_rows");
+    out = m;
+    packed_bytes_ += (int64_t)bytes;
+    packed_raw_rows_ += nraw;
+    ++packed_mats_;
+  }
+
+  // CAKE_PACK16: 0 = off, 1 = required, unset = every matrix that fits (docs/ENV.md);
+  // CAKE_PACK16_KINDS: which kinds (qkv,o,gu,down,head; default: those adopted — see
+  // profiles/pack13_decode_tuning_sweep.jsonl).  bf16, 16-bit formats, one rank per layer.
+  void pack13_all() {
+    const char* e = std::getenv("CAKE_PACK16");
+    const std::string mode = e ? e : "";
+    if (mode == "0") return;
+    const bool required = mode == "1";
+    if (!mode.empty() && !required) throw Error("CAKE_PACK16 must be 0, 1 or unset, not " + mode);
+    if (dt_ != 0 || tp_ > 1) {
+      if (required)
+        throw Error("CAKE_PACK16=1: the 13-bit packing is of bf16 weights without tensor "
+                    "parallelism; unset it (or 0) for f16 and tensor-parallel engines");
+      return;
+    }
+    const char* ke = std::getenv("CAKE_PACK16_KINDS");
+    const std::string kinds = "," + std::string(ke && *ke ? ke : kPack13Kinds) + ",";
+    auto on = [&](const char* k) { return kinds.find("," + std::string(k) + ",") != std::string::npos; };
+    const Cfg& c = lc_;
+    const size_t H = c.H, nq = (size_t)c.nh * c.hd, nk = (size_t)c.nkv * c.hd, I = c.I;
+    if (wfmt_ == 0)
+      for (LayerW& w : layers_) {
+        if (on("qkv")) pack13_one(1, w.wqkv, nq + 2 * nk, H, c.hd, required, w.pqkv);
+        if (on("o")) pack13_one(0, w.wo, H, nq, 0, required, w.po);
+        if (on("gu")) pack13_one(2, w.wgu, 2 * I, H, 0, required, w.pgu);
+        if (on("down")) pack13_one(0, w.wd, H, I, 0, required, w.pd);
+      }
+    if (head_ && hfmt_ == 0 && lm_head_ && on("head"))
+      pack13_one(0, lm_head_, (size_t)c.V, H, 0, required, phead_);
+    std::fprintf(stderr,
+                 "cake engine: decode streams %d matrices packed to 13 bits (%d raw rows), "
+                 "%.2f GiB beside the 16-bit weights%s (rank %d)\n",
+                 packed_mats_, packed_raw_rows_, (double)packed_bytes_ / (double)(1 << 30),
+                 pack_full_ ? "; the rest stay 16-bit: HBM reserve reached" : "", rank());
   }
 
   size_t kv_esize() const { return kvfmt_ == kKvFp8 ? 1 : 2; }  // bytes per cache element
@@ -1890,10 +1990,18 @@ class Llama {
         k_check(cake_gemv_x16_w8(dt_, act_, w.wd, w.sd, c.I, c.H, resid_, 1, st_), "down_proj_w8");
         continue;
       }
+      // each 16-bit GEMV below runs its P13 twin when the matrix has a packed copy
+      // (pack13_all; tp_ == 1): bit-equal outputs from 13/16 of the bytes
       const uint16_t* wqkv = reinterpret_cast<const uint16_t*>(w.wqkv);
-      k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
-                                wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
-                                pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
+      if (const P13Mat& m = w.pqkv; m.planes)
+        k_check(cake_qkv_rope_p13_kvf(dt_, resid_, w.ln1, (float)c.eps, m.p(0, c.H), m.p(nq, c.H),
+                                      m.p(nq + nk, c.H), m.h(0), m.h(nq), m.h(nq + nk), m.raw,
+                                      m.raw, m.raw, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
+                                      kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope_p13");
+      else
+        k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
+                                  wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
+                                  pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
       // one split: attention + o_proj in one launch
       if (kvfmt_ != kKvFp8 && short_step_ && ao_ok_) {
         k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.wo,
@@ -1905,16 +2013,27 @@ class Llama {
         if (tp_ > 1) {
           k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, partial_, 0, st_), "o_proj");
           ar_sum();
+        } else if (w.po.planes) {
+          k_check(cake_gemv_x16_p13(dt_, attn_out_, w.po.planes, w.po.hdr, w.po.raw, nq, c.H,
+                                    resid_, 1, st_), "o_proj_p13");
         } else {
           k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, resid_, 1, st_), "o_proj");
         }
       }
       const uint16_t* wgu = reinterpret_cast<const uint16_t*>(w.wgu);
-      k_check(cake_swiglu(dt_, resid_, w.ln2, (float)c.eps, wgu, wgu + (size_t)c.I * c.H, c.H,
-                          c.I, act_, st_), "swiglu");
+      if (const P13Mat& m = w.pgu; m.planes)
+        k_check(cake_swiglu_p13(dt_, resid_, w.ln2, (float)c.eps, m.p(0, c.H), m.p(c.I, c.H),
+                                m.h(0), m.h(c.I), m.raw, m.raw, c.H, c.I, act_, st_),
+                "swiglu_p13");
+      else
+        k_check(cake_swiglu(dt_, resid_, w.ln2, (float)c.eps, wgu, wgu + (size_t)c.I * c.H, c.H,
+                            c.I, act_, st_), "swiglu");
       if (tp_ > 1) {
         k_check(cake_gemv_x16(dt_, act_, w.wd, c.I, c.H, partial_, 0, st_), "down_proj");
         ar_sum();
+      } else if (w.pd.planes) {
+        k_check(cake_gemv_x16_p13(dt_, act_, w.pd.planes, w.pd.hdr, w.pd.raw, c.I, c.H, resid_, 1,
+                                  st_), "down_proj_p13");
       } else {
         k_check(cake_gemv_x16(dt_, act_, w.wd, c.I, c.H, resid_, 1, st_), "down_proj");
       }
@@ -1943,6 +2062,12 @@ class Llama {
                                     logits_, hist_, hist_len_, last_n, m.penalty, slot_,
                                     sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
                 "head_select_w4");
+      else if (phead_.planes)
+        k_check(cake_head_select_p13(dt_, resid_, norm_, (float)c.eps, phead_.planes, phead_.hdr,
+                                     phead_.raw, c.H, c.V, logits_, hist_, hist_len_, last_n,
+                                     m.penalty, slot_, sel_ticket_, tok_, pos_, S_, embed_, resid_,
+                                     st_),
+                "head_select_p13");
       else
         k_check(cake_head_select(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_,
                                  hist_, hist_len_, last_n, m.penalty, slot_, sel_ticket_, tok_,
@@ -1965,6 +2090,9 @@ class Llama {
     else if (hfmt_ == 2)
       k_check(cake_gemv_norm_f32_w4(dt_, row, norm_, (float)c.eps, head_q_, head_e_, c.H, c.V,
                                     logits_, st_), "lm_head_w4");
+    else if (phead_.planes)
+      k_check(cake_gemv_norm_f32_p13(dt_, row, norm_, (float)c.eps, phead_.planes, phead_.hdr,
+                                     phead_.raw, c.H, c.V, logits_, st_), "lm_head_p13");
     else
       k_check(cake_gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
               "lm_head");
@@ -3132,6 +3260,10 @@ CAKE_API int64_t cake_engine_kv_bytes(void* h) {
 
 CAKE_API int64_t cake_engine_weight_bytes(void* h) {
   return h ? static_cast<Llama*>(h)->weight_bytes() : 0;
+}
+
+CAKE_API int64_t cake_engine_packed_bytes(void* h) {
+  return h ? static_cast<Llama*>(h)->packed_bytes() : 0;
 }
 
 CAKE_API int32_t cake_engine_eos(void* h, int32_t* out, int32_t cap) {

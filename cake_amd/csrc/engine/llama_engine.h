@@ -164,6 +164,9 @@ int32_t cake_engine_eos(void* engine, int32_t* out, int32_t cap);
 // projections and their scales (weight_fmt 1: f32 per row; 2: one byte per 32 elements),
 // the quantised head and its scales (head_fmt 1, 2: also when the embeddings are tied)
 int64_t cake_engine_weight_bytes(void* engine);
+// bytes of the packed (lossless 13-bit) copies of bf16 projections / lm_head this rank keeps
+// beside the weights for its decode GEMVs (CAKE_PACK16, docs/ENV.md); not in weight_bytes
+int64_t cake_engine_packed_bytes(void* engine);
 // bytes of one session's K + V cache allocation on this rank:
 // 2 * local layers * nkv * max_seq * hd * (kv_fmt 1 ? 1 : 2)
 int64_t cake_engine_kv_bytes(void* engine);

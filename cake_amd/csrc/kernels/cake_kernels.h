@@ -189,6 +189,34 @@ int cake_swiglu(int dt, const float* resid, const void* norm_w, float eps, const
 int cake_gemv_x16(int dt, const void* x, const void* w, int K, int N, float* out, int accumulate,
                   hipStream_t st);
 
+// ---- kernels/gemv_p13.hip: lossless 13-bit bf16 projections (with pack13.hip) ----------
+// every P13 weight is (planes, row headers, raw rows or null); bf16 only, K % 2048 == 0
+int cake_gemv_p13_set_tuning(int kind, int U, int prefetch, int max_blocks);
+int cake_gemv_p13_get_tuning(int kind, int* out3);
+int cake_qkv_rope_p13_kvf(int dt, const float* resid, const void* norm_w, float eps,
+                          const void* pq, const void* pk, const void* pv, const int* hq,
+                          const int* hk, const int* hv, const void* rq, const void* rk,
+                          const void* rv, int K, int nh, int nkv, int hd, const float* inv_freq,
+                          const int* pos, float* q_out, void* kcache, void* vcache, int S,
+                          hipStream_t st, int kv_fmt);
+
+// ---- kernels/gemv_p13_head.hip: the packed lm_head -------------------------------------
+int cake_gemv_norm_f32_p13(int dt, const float* resid, const void* norm_w, float eps,
+                           const void* planes, const int* hdr, const void* raw, int K, int N,
+                           float* out, hipStream_t st);
+int cake_head_select_p13(int dt, const float* resid, const void* norm_w, float eps,
+                         const void* planes, const int* hdr, const void* raw, int K, int N,
+                         float* out, int* hist, int* hist_len, int last_n, float penalty,
+                         unsigned long long* slot, unsigned int* ticket, int* tok, int* pos,
+                         int max_hist, const void* embed, float* emb_out, hipStream_t st);
+
+// ---- kernels/gemv_p13_mlp.hip ----------------------------------------------------------
+int cake_swiglu_p13(int dt, const float* resid, const void* norm_w, float eps, const void* pg,
+                    const void* pu, const int* hg, const int* hu, const void* rg, const void* ru,
+                    int K, int I, void* act, hipStream_t st);
+int cake_gemv_x16_p13(int dt, const void* x, const void* planes, const int* hdr, const void* raw,
+                      int K, int N, float* out, int accumulate, hipStream_t st);
+
 // ---- kernels/gemv_w4.hip: MXFP4 weight-only projections (with quant_mxfp4.hip) ---------
 int cake_gemv_w4_set_tuning(int kind, int U, int prefetch, int max_blocks);
 int cake_gemv_w4_get_tuning(int kind, int* out3);
@@ -280,6 +308,16 @@ long long cake_logprob_ws_bytes(int V);
 int cake_logprob_topk(const float* logits, int V, const int32_t* tok, const int32_t* hist_len,
                       int K, void* rec, int max_rec, void* ws, unsigned int* ticket,
                       int max_blocks, hipStream_t st);
+
+// ---- kernels/pack13.hip: bf16 rows <-> their lossless 13-bit form ----------------------
+// bytes of planes | headers | nraw raw rows of a packed [N, K]; -1: K is not whole tiles
+long long cake_pack13_bytes(int N, int K, int nraw);
+// kind: a cake::PackKind (the row pairing of the reading kernel).  Returns the raw-row count
+// or a negated hipError_t; planes, hdr and raw all null: the count only.  Synchronous.
+int cake_pack13_rows(int kind, const void* rows16, int N, int K, int hd, void* planes, int* hdr,
+                     void* raw, int raw_cap, hipStream_t st);
+int cake_unpack13_rows(const void* planes, const int* hdr, const void* raw, int N, int K,
+                       void* out16, hipStream_t st);
 
 // ---- kernels/quant_fp8.hip -------------------------------------------------------------
 int cake_quant_rows_fp8(int dt, const void* w16, int N, int K, void* w8, float* scale,

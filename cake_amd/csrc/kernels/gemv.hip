@@ -26,7 +26,7 @@
 #include "gemv_kernel.h"
 
 namespace cake {
-GemvTune g_tune[3][kNumKinds] = {
+GemvTune g_tune[4][kNumKinds] = {
     // W16.  Measured in the decode graph (8B, tok/s):
     // profiles/r2_gemv_split_prologue_sweep*.jsonl — prefetching the first weight rows
     // behind the split x prologue is +10% (323 -> 357); the round-3 re-sweep
@@ -48,7 +48,12 @@ GemvTune g_tune[3][kNumKinds] = {
     // 2048; every other variation stayed under twice the 1.2 % spread of the default (x16
     // at U = 1 was -1.4 to -2 %) and was not adopted.  Nothing was swept at 70B.  The fourth
     // kind is the quantised lm_head, started from the SwiGLU values.
-    {{2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}}};
+    {{2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}, {2, 4, 1024}},
+    // P13 (gemv_p13_kernel.h): a chunk is four W16 chunks, so U 1 / prefetch 1 are W16's
+    // U 4 / prefetch 4; the grid caps are W16's but the lm_head's: at W16's 256 blocks (one
+    // wave per SIMD) the packed head ran 185 us against the 16-bit head's 155, at 512 / 1024 /
+    // 2048 blocks 133.5 / 148.7 / 136.8 (profiles/pack13_decode_tuning_sweep.jsonl)
+    {{1, 1, 1024}, {1, 1, 512}, {1, 1, 1024}, {1, 1, 512}, {1, 1, 1024}}};
 }  // namespace cake
 
 CAKE_API int cake_gemv_set_tuning(int kind, int U, int prefetch, int max_blocks) {

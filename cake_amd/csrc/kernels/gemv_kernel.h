@@ -1,9 +1,12 @@
 // Decode GEMV kernels and their launchers: one kernel family over a weight-format policy F
-// (W16 below, W8 in gemv_w8_kernel.h, W4 in gemv_w4_kernel.h).  The C entry points are
-// spread over gemv*.hip so the many (format, dtype, U, prefetch, NX) instantiations compile
-// in parallel.  Design notes: gemv.hip.  One (kind, format) is not of the family: the MXFP4
-// 16-bit-input GEMV keeps its own kernel and pair loop (gemv_w4_x16.hip says why).
+// (W16 below, W8 in gemv_w8_kernel.h, W4 in gemv_w4_kernel.h, P13 in gemv_p13_kernel.h).
+// The C entry points are spread over gemv*.hip so the many (format, dtype, U, prefetch, NX)
+// instantiations compile in parallel.  Design notes: gemv.hip.  One (kind, format) is not of
+// the family: the MXFP4 16-bit-input GEMV keeps its own kernel and pair loop
+// (gemv_w4_x16.hip says why).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace cake {
@@ -22,7 +25,7 @@ struct GemvTune { int U, PF, MB; };
 // K <= 8192 (o_proj); the quantised formats have the first four kinds
 enum GemvKind { kQkv = 0, kSwiglu = 1, kX16 = 2, kNormF32 = 3, kX16S = 4, kNumKinds = 5 };
 // the run-time tuning tables [F::kFmt][kind] (defined in gemv.hip, set by cake_gemv*_set_tuning)
-extern GemvTune g_tune[3][kNumKinds];
+extern GemvTune g_tune[4][kNumKinds];
 
 // ---------------------------------------------------------------------------
 // Weight formats.  A policy F supplies what differs between the formats:
@@ -40,6 +43,9 @@ extern GemvTune g_tune[3][kNumKinds];
 //   Rows, rows()          the pair of rows a wave works on
 //   Chunk, load<NT>()     one chunk of both rows (NT: non-temporal, the main loop)
 //   fma<DT, XF32>()       acc += chunk . x
+//   kRawRows (optional)   Rows carries per-row state read from memory (run_pairs takes a wave's
+//                         first rows from the prefetch registers, not from a second map()), and
+//                         is_raw() / raw_rows(): a pair kept as plain 16-bit rows runs W16's loop
 // ---------------------------------------------------------------------------
 
 // the q / k / v pointer of pair kind 0 / 1 / 2 by address arithmetic, not a pointer select:
@@ -112,6 +118,22 @@ struct W16 : PlainRows {
     }
   }
 };
+
+template <class F, class = void> struct HasRawRows : std::false_type {};
+template <class F>
+struct HasRawRows<F, std::void_t<decltype(F::kRawRows)>> : std::bool_constant<F::kRawRows> {};
+
+template <class F, class = void> struct Bf16Only : std::false_type {};
+template <class F>
+struct Bf16Only<F, std::void_t<decltype(F::kBf16Only)>> : std::bool_constant<F::kBf16Only> {};
+
+// The occupancy (waves per SIMD) the register allocator is asked to keep for the 16-bit-input
+// GEMV of a format at U chunks in flight: x16_waves(U) where the format has one, else 1, the
+// compiler's own floor.
+template <class F, int U, class = void> struct X16Waves : std::integral_constant<int, 1> {};
+template <class F, int U>
+struct X16Waves<F, U, std::void_t<decltype(F::x16_waves(U))>>
+    : std::integral_constant<int, F::x16_waves(U)> {};
 
 // The epilogue scale hook.  kRowScale (fp8): the first pair's row scales are requested in
 // the prologue slot (row_scale) and every wave sum is multiplied by its row's (descale);
@@ -254,7 +276,13 @@ __device__ __forceinline__ void dot_range(const typename F::Rows& r, const void*
 }
 
 // prefetch registers: PFC chunks of the pair per lane
-template <class F, int PFC> struct Regs { typename F::Chunk c[PFC > 0 ? PFC : 1]; };
+template <class F, int PFC, bool RAW = HasRawRows<F>::value> struct Regs {
+  typename F::Chunk c[PFC > 0 ? PFC : 1];
+};
+template <class F, int PFC> struct Regs<F, PFC, true> {
+  typename F::Chunk c[PFC > 0 ? PFC : 1];
+  typename F::Rows r;  // the rows prefetch_rows was given
+};
 
 // issue the first PFC chunks of the pair (nch >= 64 PFC)
 template <class F, int PFC>
@@ -266,12 +294,77 @@ __device__ __forceinline__ void prefetch_rows(const typename F::Rows& r, Regs<F,
   }
 }
 
+// kRawRows: keep the (clamped) first pair's rows, whose headers are already requested, for
+// run_pairs_raw.  Every wave does, prefetching or not: choosing between these rows and fresh
+// ones there made the compiler pick through memory (48 bytes of scratch per lane).
+template <class F, int PFC>
+__device__ __forceinline__ void keep_rows(const typename F::Rows& r, Regs<F, PFC>& g) {
+  if constexpr (HasRawRows<F>::value) g.r = r;
+}
+
+// run_pairs of a kRawRows format.  A pair kept as plain 16-bit rows takes its dot products
+// from W16's loop (the same per-lane order whatever W16's U); the branch is wave-uniform and
+// stands once per pair, in front of two complete code paths, each with its own epilogue call.
+// A pair's rows (its headers) are asked for one pair ahead, while the pair before streams.
+template <class F, int DT, bool XF32, int U, int PFC, class Map, class Epi>
+__device__ __forceinline__ void run_pairs_raw(const Map& map, const Epi& epi, const void* xs, int K,
+                                              int npairs, int p0, int stride,
+                                              const Regs<F, PFC>& pre) {
+  const int nch = K >> F::kLog2;
+  auto raw_dots = [&](const typename F::Rows& r, float& aa, float& ab) {
+    dot_range<W16, DT, XF32, 4>(F::raw_rows(r, K), xs, K >> W16::kLog2, 0, aa, ab);
+  };
+  auto clamped = [&](int q) { return map(q < npairs ? q : npairs - 1); };
+  int p = p0;
+  typename F::Rows rn;
+  if constexpr (PFC > 0) {
+    // the rows keep_rows was given: the wave's first pair, clamped (an idle wave of a kernel
+    // without the split prologue has prefetched nothing: it works on the last pair and drops it)
+    const typename F::Rows r = pre.r;
+    rn = clamped(p + stride);
+    const int lane = threadIdx.x & 63;
+    if (F::is_raw(r)) {  // (the prefetched planes are dropped)
+      float aa = 0.f, ab = 0.f;
+      raw_dots(r, aa, ab);
+      const float sa = wave_sum(aa), sb = wave_sum(ab);
+      if (p < npairs) epi(p, sa, sb);
+    } else {
+      typename F::Acc aa = F::zero(), ab = F::zero();
+#pragma unroll
+      for (int c = 0; c < PFC; ++c) F::template fma<DT, XF32>(xs, c * 64 + lane, pre.c[c], aa, ab);
+      dot_range<F, DT, XF32, U>(r, xs, nch, PFC * 64, aa, ab);
+      const float sa = wave_sum(F::total(aa)), sb = wave_sum(F::total(ab));
+      if (p < npairs) epi(p, sa, sb);
+    }
+    p += stride;
+  } else {
+    rn = clamped(p);
+  }
+  for (; p < npairs; p += stride) {
+    const typename F::Rows r = rn;
+    rn = clamped(p + stride);
+    if (F::is_raw(r)) {
+      float aa = 0.f, ab = 0.f;
+      raw_dots(r, aa, ab);
+      epi(p, wave_sum(aa), wave_sum(ab));
+      continue;
+    }
+    typename F::Acc aa = F::zero(), ab = F::zero();
+    dot_range<F, DT, XF32, U>(r, xs, nch, 0, aa, ab);
+    epi(p, wave_sum(F::total(aa)), wave_sum(F::total(ab)));
+  }
+}
+
 // Walk the wave's pairs p0, p0+stride, ...: map(p) gives the rows, epi(p, da, db)
 // consumes the two dot products (full wave sums; kRowScale: not yet scaled).
 template <class F, int DT, bool XF32, int U, int PFC, class Map, class Epi>
 __device__ __forceinline__ void run_pairs(const Map& map, const Epi& epi, const void* xs, int K,
                                           int npairs, int p0, int stride,
                                           const Regs<F, PFC>& pre) {
+  if constexpr (HasRawRows<F>::value) {
+    run_pairs_raw<F, DT, XF32, U, PFC>(map, epi, xs, K, npairs, p0, stride, pre);
+    return;
+  }
   const int nch = K >> F::kLog2;
   int p = p0;
   if constexpr (PFC > 0) {
@@ -348,6 +441,7 @@ __global__ __launch_bounds__(kGemvThreads) void qkv_rope_kernel(QkvArgs<F> a) {
   NormPre<F, DT, NX> xp;
   const int pc = p0 < npairs ? p0 : npairs - 1;
   const typename F::Rows r0 = map(pc);  // rows first: their address math may load (kernarg select)
+  keep_rows<F, PFC>(r0, pre);
   if constexpr (NX > 0) xp.load(a.resid, a.norm_w, a.K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
   if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
@@ -407,6 +501,7 @@ __global__ __launch_bounds__(kGemvThreads) void swiglu_kernel(
   NormPre<F, DT, NX> xp;
   const int jp = j0 < I ? j0 : I - 1;
   const typename F::Rows r0 = map(jp);
+  keep_rows<F, PFC>(r0, pre);
   if constexpr (NX > 0) xp.load(resid, norm_w, K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
   // NX: unconditional (an idle wave re-reads the last row), so the vmcnt is exact
@@ -429,7 +524,8 @@ __global__ __launch_bounds__(kGemvThreads) void swiglu_kernel(
 // residual stream) — or plain f32 output.
 // ---------------------------------------------------------------------------
 template <class F, int DT, int U, int PFC, int NX, bool ACCUM>
-__global__ __launch_bounds__(kGemvThreads) void gemv_x16_kernel(
+__global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(X16Waves<F, U>::value)))
+void gemv_x16_kernel(
     const uint16_t* __restrict__ x, const typename F::Mat w, int K, int N,
     float* __restrict__ out) {
   extern __shared__ float smem[];
@@ -442,6 +538,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_x16_kernel(
   Plain16Pre<F, NX> xp;
   const int pc = p0 < npairs ? p0 : npairs - 1;
   const typename F::Rows r0 = map(pc);
+  keep_rows<F, PFC>(r0, pre);
   if constexpr (NX > 0) xp.load(x, K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
   if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
@@ -603,6 +700,7 @@ __global__ __launch_bounds__(kGemvThreads) void gemv_norm_f32_kernel(
   NormPre<F, DT, NX> xp;
   const int pc = p0 < npairs ? p0 : npairs - 1;
   const typename F::Rows r0 = map(pc);
+  keep_rows<F, PFC>(r0, pre);
   if constexpr (NX > 0) xp.load(resid, norm_w, K);
   __builtin_amdgcn_sched_barrier(0);  // x loads strictly before the weights (in-order vmcnt)
   if (NX > 0 || (PFC > 0 && p0 < npairs)) prefetch_rows<F, PFC>(r0, pre);  // NX: exact vmcnt
@@ -648,6 +746,14 @@ using namespace cake;
     if ((dt) == kBF16) { constexpr int DT = kBF16; __VA_ARGS__; } \
     else if ((dt) == kF16) { constexpr int DT = kF16; __VA_ARGS__; } \
     else return (int)hipErrorInvalidValue;         \
+  } while (0)
+// the launchers' form: a format of bf16 rows alone (kBf16Only) has no f16 kernels
+#define DISPATCH_DT_F(F, dt, ...)                  \
+  do {                                             \
+    if constexpr (Bf16Only<F>::value) {            \
+      if ((dt) == kBF16) { constexpr int DT = kBF16; __VA_ARGS__; } \
+      else return (int)hipErrorInvalidValue;       \
+    } else DISPATCH_DT(dt, __VA_ARGS__);           \
   } while (0)
 
 // Expand BODY for the run-time (U, PF) choice among those format F instantiates: t.U is one
@@ -719,7 +825,7 @@ template <class F> static int launch_qkv(int dt, const QkvArgs<F>& a, hipStream_
   const int K = a.K, npairs = (a.nh + 2 * a.nkv) * (a.hd / 2);
   const size_t lds = x32_lds_bytes<F>(K);
   const GemvTune t = g_tune[F::kFmt][kQkv];
-  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((qkv_rope_kernel<F, DT, U, PF, NX>),
+  DISPATCH_DT_F(F, dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((qkv_rope_kernel<F, DT, U, PF, NX>),
                                                          dim3(grid_for(npairs, t.MB)),
                                                          dim3(kGemvThreads), lds, st, a))));
   return (int)hipGetLastError();
@@ -735,7 +841,7 @@ static int launch_swiglu(int dt, const float* resid, const void* norm_w, float e
   // at least one block per 28 rows (7 row pairs per wave): 70B's I = 28672 runs 1024
   // blocks (+0.7 %, profiles/r2_decode_gemv_tuning_70b.jsonl), 8B's 14336 the tuned cap
   const int mb = t.MB > (I + 27) / 28 ? t.MB : (I + 27) / 28;
-  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((swiglu_kernel<F, DT, U, PF, NX>),
+  DISPATCH_DT_F(F, dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((swiglu_kernel<F, DT, U, PF, NX>),
                                                          dim3(grid_for(I, mb)), dim3(kGemvThreads),
                                                          lds, st, resid, (const uint16_t*)norm_w, eps,
                                                          wg, wu, K, I, (uint16_t*)act))));
@@ -750,11 +856,11 @@ static int launch_x16(int dt, const void* x, typename F::Mat w, int K, int N, fl
   const GemvTune t = g_tune[F::kFmt][F::kKinds > kX16S && K <= 8192 ? kX16S : kX16];
   const int g = grid_for((N + 1) / 2, t.MB);
   if (accumulate) {
-    DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, true>),
+    DISPATCH_DT_F(F, dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, true>),
                                                           dim3(g), dim3(kGemvThreads), lds, st,
                                                           (const uint16_t*)x, w, K, N, out))));
   } else {
-    DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, false>),
+    DISPATCH_DT_F(F, dt, DISPATCH_TUNE(F, t, K, CAKE_NX_X16(K, hipLaunchKernelGGL((gemv_x16_kernel<F, DT, U, PF, NX, false>),
                                                           dim3(g), dim3(kGemvThreads), lds, st,
                                                           (const uint16_t*)x, w, K, N, out))));
   }
@@ -769,7 +875,7 @@ static int launch_norm_f32(int dt, const float* resid, const void* norm_w, float
   // SEL: at least the 64 bytes head_sel_tail keeps its words in (a 16-bit K of 8)
   const size_t lds = SEL && x32_lds_bytes<F>(K) < 64 ? 64 : x32_lds_bytes<F>(K);
   const GemvTune t = g_tune[F::kFmt][kNormF32];
-  DISPATCH_DT(dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((gemv_norm_f32_kernel<F, DT, U, PF, NX, SEL>),
+  DISPATCH_DT_F(F, dt, DISPATCH_TUNE(F, t, K, CAKE_NX_NORM(K, hipLaunchKernelGGL((gemv_norm_f32_kernel<F, DT, U, PF, NX, SEL>),
                                                          dim3(grid_for((N + 1) / 2, t.MB)),
                                                          dim3(kGemvThreads), lds, st, resid,
                                                          (const uint16_t*)norm_w, eps, w, K, N,

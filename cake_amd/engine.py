@@ -94,6 +94,8 @@ def _bind(L) -> None:
     L.cake_engine_eos.restype = I
     L.cake_engine_weight_bytes.argtypes = [P]
     L.cake_engine_weight_bytes.restype = C.c_int64
+    L.cake_engine_packed_bytes.argtypes = [P]
+    L.cake_engine_packed_bytes.restype = C.c_int64
     L.cake_engine_kv_bytes.argtypes = [P]
     L.cake_engine_kv_bytes.restype = C.c_int64
     L.cake_engine_open_layers.argtypes = [C.c_char_p, C.POINTER(EngineOpts),
@@ -343,6 +345,12 @@ class NativeLlama:
         ``"mxfp4"``: one byte per 32 elements), and a quantised head with its scales
         (``head="fp8"`` / ``"mxfp4"``; counted also when the embeddings are tied)."""
         return int(lib().cake_engine_weight_bytes(self._h))
+
+    def packed_bytes(self) -> int:
+        """Bytes of the packed (lossless 13-bit) copies of bf16 projections and lm_head the
+        decode GEMVs of this rank stream instead of the 16-bit rows (``CAKE_PACK16``,
+        docs/ENV.md); they sit beside the weights and are not part of ``weight_bytes``."""
+        return int(lib().cake_engine_packed_bytes(self._h))
 
     def kv_bytes(self) -> int:
         """Bytes of one session's K + V cache on this rank: 2 x local layers x kv heads x

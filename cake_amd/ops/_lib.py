@@ -102,6 +102,18 @@ _SIGS = {
     # kernels/gemv_mlp.hip
     "cake_swiglu": (I, [I, P, P, F, P, P, I, I, P, P]),
     "cake_gemv_x16": (I, [I, P, P, I, I, P, I, P]),
+    # kernels/gemv_p13.hip: lossless 13-bit bf16 projections (with pack13.hip
+    "cake_gemv_p13_set_tuning": (I, [I, I, I, I]),
+    "cake_gemv_p13_get_tuning": (I, [I, P]),
+    "cake_qkv_rope_p13_kvf": (I, [I, P, P, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P,
+                                  P, I, P, I]),
+    # kernels/gemv_p13_head.hip: the packed lm_head
+    "cake_gemv_norm_f32_p13": (I, [I, P, P, F, P, P, P, I, I, P, P]),
+    "cake_head_select_p13": (I, [I, P, P, F, P, P, P, I, I, P, P, P, I, F, P, P, P, P, I, P, P,
+                                 P]),
+    # kernels/gemv_p13_mlp.hip
+    "cake_swiglu_p13": (I, [I, P, P, F, P, P, P, P, P, P, I, I, P, P]),
+    "cake_gemv_x16_p13": (I, [I, P, P, P, P, I, I, P, I, P]),
     # kernels/gemv_w4.hip: MXFP4 weight-only projections (with quant_mxfp4.hip
     "cake_gemv_w4_set_tuning": (I, [I, I, I, I]),
     "cake_gemv_w4_get_tuning": (I, [I, P]),
@@ -143,6 +155,10 @@ _SIGS = {
     # kernels/logprob.hip: log-probs of a generated token
     "cake_logprob_ws_bytes": (L, [I]),
     "cake_logprob_topk": (I, [P, I, P, P, I, P, I, P, P, I, P]),
+    # kernels/pack13.hip: bf16 rows <-> their lossless 13-bit form
+    "cake_pack13_bytes": (L, [I, I, I]),
+    "cake_pack13_rows": (I, [I, P, I, I, I, P, P, P, I, P]),
+    "cake_unpack13_rows": (I, [P, P, P, I, I, P, P]),
     # kernels/quant_fp8.hip
     "cake_quant_rows_fp8": (I, [I, P, I, I, P, P, P]),
     "cake_dequant_rows_fp8": (I, [I, P, P, I, I, P, P]),

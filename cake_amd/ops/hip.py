@@ -963,6 +963,181 @@ def get_gemv_w8_tuning(kind: str) -> tuple[int, int, int]:
 
 
 # ---------------------------------------------------------------------------
+# P13: bf16 rows packed losslessly into 13 bits per value (pack13.hip, gemv_p13*.hip; the
+# format is written down in csrc/kernels/gemv_p13_kernel.h).  K % 2048 == 0, bf16 only; the
+# argument rules are the library's (a call that breaks one raises KernelError).
+# ---------------------------------------------------------------------------
+
+PACK13_TILE, PACK13_TILE_BYTES = 2048, 3328
+PACK13_KINDS = {"adjacent": 0, "head_halves": 1, "gate_up": 2}
+
+
+def pack13_bytes(N: int, K: int, nraw: int) -> int:
+    """Bytes of planes | headers | raw rows of a packed [N, K]; -1: K is not whole tiles."""
+    return int(kernels().cake_pack13_bytes(int(N), int(K), int(nraw)))
+
+
+class Packed13:
+    """A packed matrix: planes uint8 [N, K * 13 / 8], hdr int32 [N], raw bf16 [nraw, K] or
+    None.  `rows(lo, hi)` is the sub-matrix of those rows (a view: q / k / v, gate / up)."""
+
+    def __init__(self, planes, hdr, raw, K: int):
+        self.planes, self.hdr, self.raw, self.K = planes, hdr, raw, int(K)
+
+    @property
+    def N(self) -> int:
+        return self.hdr.numel()
+
+    @property
+    def nraw(self) -> int:
+        return 0 if self.raw is None else self.raw.shape[0]
+
+    def rows(self, lo: int, hi: int) -> "Packed13":
+        return Packed13(self.planes[lo:hi], self.hdr[lo:hi], self.raw, self.K)
+
+    def args(self):
+        return _p(self.planes), _p(self.hdr), _p(self.raw)
+
+
+def _req_p13(m: Packed13, name: str, N: int, K: int) -> None:
+    _req(m.planes, name + " planes", dtype=torch.uint8, numel=N * (K // 8) * 13)
+    _req(m.hdr, name + " hdr", dtype=torch.int32, shape=(N,))
+    if m.raw is not None:
+        _req(m.raw, name + " raw", dtype=torch.bfloat16)
+    if m.K != K:
+        raise ValueError(f"{name}: packed with K = {m.K}, not {K}")
+
+
+def pack13_rows(w16, kind: str = "adjacent", hd: int = 0) -> Packed13:
+    """Pack bf16 rows [N, K] for the kernel kind that will read them (its row pairing:
+    PACK13_KINDS; `hd` = the head dimension of "head_halves").  Synchronous."""
+    N, K = w16.shape
+    _req(w16, "w16")
+    k, st = PACK13_KINDS[kind], _stream()
+    nraw = kernels().cake_pack13_rows(k, _p(w16), N, K, int(hd), None, None, None, 0, st)
+    check(-nraw if nraw < 0 else 0, "pack13_rows")
+    planes = torch.zeros((N, K // PACK13_TILE * PACK13_TILE_BYTES), dtype=torch.uint8,
+                         device=w16.device)
+    hdr = torch.zeros(N, dtype=torch.int32, device=w16.device)
+    raw = torch.zeros((nraw, K), dtype=w16.dtype, device=w16.device) if nraw else None
+    got = kernels().cake_pack13_rows(k, _p(w16), N, K, int(hd), _p(planes), _p(hdr), _p(raw),
+                                     nraw, st)
+    check(-got if got < 0 else 0, "pack13_rows")
+    assert got == nraw, (got, nraw)
+    return Packed13(planes, hdr, raw, K)
+
+
+def unpack13_rows(m: Packed13, out16) -> None:
+    """out16 [N, K] bf16 = the rows `m` was packed from, bit for bit."""
+    N, K = out16.shape
+    _req_p13(m, "m", N, K)
+    _req(out16, "out16", dtype=torch.bfloat16)
+    check(kernels().cake_unpack13_rows(*m.args(), N, K, _p(out16), _stream()), "unpack13_rows")
+
+
+def qkv_rope_p13(resid, norm_w, eps, mq: Packed13, mk: Packed13, mv: Packed13, inv_freq, pos,
+                 q_out, kcache, vcache, kv_fmt=0):
+    """:func:`qkv_rope` over packed weights (every output bit-equal to it)."""
+    K = resid.numel()
+    nkv, S, hd = kcache.shape
+    nh = mq.N // hd
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_p13(mq, "wq", nh * hd, K)
+    _req_p13(mk, "wk", nkv * hd, K)
+    _req_p13(mv, "wv", nkv * hd, K)
+    _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
+    _req(pos, "pos", dtype=torch.int32, numel=1)
+    _req(q_out, "q_out", dtype=torch.float32, numel=nh * hd)
+    _req(kcache, "kcache", dtype=_kv_cache_dtype(kv_fmt, norm_w.dtype))
+    _req(vcache, "vcache", dtype=kcache.dtype, shape=kcache.shape)
+    (pq, hq, rq), (pk, hk, rk), (pv, hv, rv) = mq.args(), mk.args(), mv.args()
+    check(kernels().cake_qkv_rope_p13_kvf(_dt(norm_w), _p(resid), _p(norm_w), float(eps), pq, pk,
+                                          pv, hq, hk, hv, rq, rk, rv, K, nh, nkv, hd,
+                                          _p(inv_freq), _p(pos), _p(q_out), _p(kcache),
+                                          _p(vcache), S, _stream(), int(kv_fmt)),
+          "qkv_rope_p13_kvf")
+
+
+def swiglu_p13(resid, norm_w, eps, mg: Packed13, mu: Packed13, act):
+    """:func:`swiglu` over packed weights."""
+    K = resid.numel()
+    I = mg.N
+    _req(resid, "resid", dtype=torch.float32)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req_p13(mg, "wg", I, K)
+    _req_p13(mu, "wu", I, K)
+    _req(act, "act", dtype=norm_w.dtype, numel=I)
+    (pg, hg, rg), (pu, hu, ru) = mg.args(), mu.args()
+    check(kernels().cake_swiglu_p13(_dt(norm_w), _p(resid), _p(norm_w), float(eps), pg, pu, hg,
+                                    hu, rg, ru, K, I, _p(act), _stream()), "swiglu_p13")
+
+
+def gemv_p13(x, m: Packed13, out, accumulate: bool):
+    """out (f32) [+]= W @ x with a 16-bit x (batch 1) over packed weights."""
+    N, K = m.N, x.numel()
+    _req_p13(m, "w", N, K)
+    _req(x, "x", numel=K)
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_x16_p13(_dt(x), _p(x), *m.args(), K, N, _p(out), int(accumulate),
+                                      _stream()), "gemv_x16_p13")
+
+
+def norm_gemv_f32_p13(resid, norm_w, eps, m: Packed13, out):
+    """out (f32) = W @ rmsnorm(resid) over packed weights — the lm_head (batch 1)."""
+    N, K = m.N, resid.numel()
+    _req_p13(m, "w", N, K)
+    _req(resid, "resid", dtype=torch.float32, numel=K)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req(out, "out", dtype=torch.float32, numel=N)
+    check(kernels().cake_gemv_norm_f32_p13(_dt(norm_w), _p(resid), _p(norm_w), float(eps),
+                                           *m.args(), K, N, _p(out), _stream()),
+          "gemv_norm_f32_p13")
+
+
+def head_select_p13(resid, norm_w, eps, m: Packed13, logits, hist, hist_len, last_n: int,
+                    penalty: float, slot, ticket, tok, pos, embed=None) -> None:
+    """:func:`head_select` over the packed head; `embed` stays the 16-bit table."""
+    N, K = m.N, resid.numel()
+    _req_p13(m, "w", N, K)
+    _req(resid, "resid", dtype=torch.float32, numel=K)
+    _req(norm_w, "norm_w", shape=(K,))
+    _req(logits, "logits", dtype=torch.float32, numel=N)
+    _req(slot, "slot", dtype=torch.int64, numel=1)
+    _req(ticket, "ticket", dtype=torch.int32, numel=1)
+    for t, n in ((tok, "tok"), (hist, "hist"), (hist_len, "hist_len"), (pos, "pos")):
+        _req(t, n, dtype=torch.int32)
+    if not 0 <= int(last_n) <= HEAD_SELECT_MAX_LAST_N:
+        raise ValueError(f"head_select_p13: last_n {last_n} > {HEAD_SELECT_MAX_LAST_N}")
+    if embed is not None:
+        _req(embed, "embed", dtype=norm_w.dtype)
+        if embed.dim() != 2 or embed.shape[1] != K:
+            raise ValueError(f"head_select_p13: embed {tuple(embed.shape)} does not match H={K}")
+    check(kernels().cake_head_select_p13(
+        _dt(norm_w), _p(resid), _p(norm_w), float(eps), *m.args(), K, N, _p(logits), _p(hist),
+        _p(hist_len), int(last_n), float(penalty), _p(slot), _p(ticket), _p(tok), _p(pos),
+        hist.numel(), None if embed is None else _p(embed),
+        None if embed is None else _p(resid), _stream()), "head_select_p13")
+
+
+GEMV_P13_KINDS = {"qkv": 0, "swiglu": 1, "x16": 2, "head": 3, "x16s": 4}
+GEMV_P13_U, GEMV_P13_PF = (1, 2, 3), (0, 1, 2)
+
+
+def set_gemv_p13_tuning(kind: str, U: int = 1, prefetch: int = 1, max_blocks: int = 1024) -> None:
+    """Launch geometry of one packed GEMV kind (gemv_p13.hip): U in {1, 2, 3} tiles per row in
+    flight, prefetch in {0, 1, 2} tiles per row; "x16s" = the 16-bit-input GEMV at K <= 8192."""
+    check(kernels().cake_gemv_p13_set_tuning(GEMV_P13_KINDS[kind], int(U), int(prefetch),
+                                             int(max_blocks)), "gemv_p13_set_tuning")
+
+
+def get_gemv_p13_tuning(kind: str) -> tuple[int, int, int]:
+    out = (C.c_int * 3)()
+    check(kernels().cake_gemv_p13_get_tuning(GEMV_P13_KINDS[kind], out), "gemv_p13_get_tuning")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+# ---------------------------------------------------------------------------
 # MXFP4 weight-only projections: w4 [N, K/2] uint8 (two e2m1 codes per byte, k even in the
 # low nibble) + e8 [N, K/32] uint8 e8m0 block scales,
 # W[n, k] = 2^(e8[n, k/32] - 127) * e2m1(code); K % 32 == 0 (quant_mxfp4.hip, gemv_w4*.hip).
