@@ -473,7 +473,7 @@ CAKE_API int cake_sum_slices(float* out, const float* src, int W, long long stri
   if (W < 1 || n < 0 || stride < n || (stride % 4) || ((uintptr_t)out % 16) || ((uintptr_t)src % 16))
     return (int)hipErrorInvalidValue;
   if (n == 0) return 0;
-  long long g = (n / 4 + 255) / 256;
+  long long g = ((n + 3) / 4 + 255) / 256;  // threads take 4 elements; n < 4 still needs a block
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)g), dim3(256), 0, st, out, src, W, stride, n,
                      accumulate);

@@ -37,10 +37,22 @@ __device__ __forceinline__ uint4 philox4(uint32_t c0, uint32_t c1, uint32_t k0, 
   return make_uint4(c0, c1, c2, c3);
 }
 
+// logf / cosf, not the fast forms: those are off by up to 1.7e-6 whatever |z| is (measured),
+// which next to a zero of the cosine is many times the sample itself
 __device__ __forceinline__ float normal_from(uint32_t a, uint32_t b) {
   const float u1 = ((float)(a >> 8) + 0.5f) * 5.9604644775390625e-08f;  // (0, 1]: 1.0 for the largest a >> 8 (a zero sample)
   const float u2 = (float)(b >> 8) * 5.9604644775390625e-08f;
-  return sqrtf(-2.f * __logf(u1)) * __cosf(6.283185307179586f * u2);
+  return sqrtf(-2.f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// a * b rounded to f32 before anything else happens to it.  Without this the f16 stores
+// below fuse the product into their conversion (v_fma_mixlo_f16: one rounding of the exact
+// product), and the f16 engine's UNet input differs in rare last bits from the bf16 form's
+// and from torch's (x * s).to(f16), which round twice.
+__device__ __forceinline__ float mul_f32(float a, float b) {
+  float p = a * b;
+  asm volatile("" : "+v"(p));  // the compiler folds the product into the conversion otherwise
+  return p;
 }
 
 template <int DT, bool OUT16>
@@ -84,7 +96,7 @@ __global__ void sched_step_kernel(float* __restrict__ x, const uint16_t* __restr
     }
     x[i] = y;
     if (next_in != nullptr) {
-      const uint16_t v = from_f32<DT>(y * c.w);
+      const uint16_t v = from_f32<DT>(mul_f32(y, c.w));
       next_in[i] = v;
       if (cfg) next_in[i + n] = v;
     }
@@ -99,7 +111,7 @@ __global__ void scale_copy_kernel(const float* __restrict__ x, long long n, floa
                                   uint16_t* __restrict__ out) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
-    const uint16_t v = from_f32<DT>(x[i] * scale);
+    const uint16_t v = from_f32<DT>(mul_f32(x[i], scale));
     out[i] = v;
     if (dup) out[i + n] = v;
   }

@@ -603,6 +603,30 @@ def add_resid(resid, y):
           "add_resid")
 
 
+def fill_normal(out, mean: float, std: float, key: int):
+    """out (16-bit, 16-byte aligned) <- N(mean, std^2) draws that depend only on (key, element
+    index): the random-init weights of the native engines' synthetic checkpoints."""
+    _req(out, "out")
+    if out.data_ptr() % 16:
+        raise ValueError("fill_normal: out must be 16-byte aligned")
+    check(kernels().cake_fill_normal(_dt(out), _p(out), out.numel(), float(mean), float(std),
+                                     int(key) & 0xFFFFFFFFFFFFFFFF, _stream()), "fill_normal")
+
+
+def sum_slices(out, src, W: int, stride: int, n: int, accumulate: bool):
+    """out[:n] (f32) (+)= the sum over w < W of src[w * stride : w * stride + n], added in
+    that order (the tensor-parallel prefill reduction of the ranks' slab slices)."""
+    W, stride, n = int(W), int(stride), int(n)
+    if W < 1 or n < 0 or stride < n or stride % 4:
+        raise ValueError("sum_slices: W >= 1, 0 <= n <= stride and stride % 4 == 0 expected")
+    _req(out, "out", dtype=torch.float32, numel=n)
+    _req(src, "src", dtype=torch.float32, numel=(W - 1) * stride + n)
+    if out.data_ptr() % 16 or src.data_ptr() % 16:
+        raise ValueError("sum_slices: out and src must be 16-byte aligned")
+    check(kernels().cake_sum_slices(_p(out), _p(src), W, stride, n, int(bool(accumulate)),
+                                    _stream()), "sum_slices")
+
+
 def stream_read(buf, blocks, sink, nbytes=None):
     """Bandwidth probe: read ``nbytes`` (default all) of ``buf`` and nothing else."""
     _req(buf, "buf")
@@ -1274,6 +1298,15 @@ def flash_set_impl(v: int) -> None:
     kernels().cake_flash_set_impl(int(v))
 
 
+def flash_set_nw(nw: int) -> None:
+    """Waves per workgroup of the 32x32x16 flash kernel: 0 auto (4 unless the grid is tiny),
+    1 / 2 / 4 forced (tests / A-B).  A value below the kernel's minimum (1 at D > 64) is
+    ignored there."""
+    if nw not in (0, 1, 2, 4):
+        raise ValueError(f"flash_set_nw: 0, 1, 2 or 4 expected, got {nw}")
+    kernels().cake_flash_set_nw(int(nw))
+
+
 def flash_set_pair_min(n: int) -> None:
     """Causal flash (v2): pair q tiles x / n-1-x per workgroup once the unpaired grid has
     at least n workgroups (default 512; <= 0 never pairs)."""
@@ -1641,6 +1674,36 @@ def scale_copy(x, scale: float, dup: bool, out):
     _req(out, "out", numel=n * (2 if dup else 1))
     check(kernels().cake_scale_copy(_dt(out), _p(x), n, float(scale), int(dup), _p(out),
                                     _stream()), "scale_copy")
+
+
+def clip_embed(tok, pos, ids, T: int, out):
+    """out [rows, D] (16-bit) = tok[ids[r]] + pos[r % T]: the CLIP token + position embedding
+    sum, one rounding of the f32 sum.  tok [V, D], pos [>= T, D], ids int32 [rows]; an id
+    outside [0, V) is clamped into it on the device."""
+    if tok.dim() != 2 or pos.dim() != 2:
+        raise ValueError("clip_embed: tok [V, D] and pos [T, D] expected")
+    V, D = tok.shape
+    rows = ids.numel()
+    if rows < 1 or T < 1 or V < 1 or D < 1:
+        raise ValueError("clip_embed: rows, T, D and V must be positive")
+    _req(tok, "tok")
+    _req(pos, "pos", dtype=tok.dtype, numel=T * D)
+    if pos.shape[1] != D:
+        raise ValueError(f"clip_embed: pos rows of {D} expected, got {pos.shape[1]}")
+    _req(ids, "ids", dtype=torch.int32)
+    _req(out, "out", dtype=tok.dtype, numel=rows * D)
+    check(kernels().cake_clip_embed(_dt(tok), _p(tok), _p(pos), _p(ids), rows, int(T), D, V,
+                                    _p(out), _stream()), "clip_embed")
+
+
+def widen16(x, out):
+    """out (f32) <- x (16-bit), exactly."""
+    n = x.numel()
+    if n < 1:
+        raise ValueError("widen16: empty input")
+    _req(x, "x")
+    _req(out, "out", dtype=torch.float32, numel=n)
+    check(kernels().cake_widen16(_dt(x), _p(x), n, _p(out), _stream()), "widen16")
 
 
 def to_rgb8(img, nhwc: bool = False) -> torch.Tensor:

@@ -49,6 +49,8 @@ F32_FLUSH = 2.0 ** -102     # EPS24 * F32_FLUSH = 2^-126, the smallest normal f3
 # (1, 4100, 64, 8), f16, eps-visible (f32 summation error grows with the group; plain
 # two-pass f32 needs 16 there).  Everything else needs at most 4: RMSNorm 4 (H = 12288),
 # the norms, GEGLU and SiLU * up 2, RoPE 1; the conditioning sweep 4 (bf16) and 2 (f16).
+# With the Stable Diffusion families at the end of this file (611 cases per dtype): the
+# timestep embedding 16 (f16, dim 2560, t = 999), the scheduler step 2.
 YARDSTICK_K = 64
 K = 2 * YARDSTICK_K
 
@@ -558,3 +560,42 @@ def yardstick(family: str, c: dict, G: int = 1, silu: bool = False) -> torch.Ten
     else:
         y = group_norm_nhwc_yardstick(c["x"], c["gamma"], c["beta"], G, c["eps"], silu)
     return y.to(dt)
+
+
+# ---------------------------------------------------------------------------
+# Stable Diffusion step glue (references: _glue.py): the timestep embedding and the scheduler
+# step as families of the rule.  The embedding's A = |angle| reaches 999, so its A term is
+# above one output ulp at the slow frequencies by construction (the conditioning of sin / cos
+# at a large f32 argument is the point of the term): no check_cap there.
+# ---------------------------------------------------------------------------
+
+MANT[torch.float32], EMIN[torch.float32] = 23, -126     # ulp16 / allowance of an f32 output
+
+TE_FLIP_SHIFT = [(False, 0.0), (False, 1.0), (True, 0.0), (True, 1.0)]
+SCHED_CPU_N = 1000
+
+
+def timestep_embed_yardstick(t: float, B: int, dim: int, flip: bool, shift: float) -> torch.Tensor:
+    """The embedding in plain f32 torch (f32 output; round it to the case's dtype)."""
+    import _glue as G
+    return G.timestep_embed_ref(t, B, dim, flip, shift, torch.float32)[0]
+
+
+def sd_glue_cases(dt):
+    """(family, name, case, f32 yardstick rounded to dt) of the two Stable Diffusion families,
+    for test_ulp_cpu.py::test_yardstick_k."""
+    import _glue as G
+    for dim in G.TE_DIMS:
+        for flip, shift in TE_FLIP_SHIFT:
+            for t in G.TE_TABLE:
+                ref, A = G.timestep_embed_ref(t, 1, dim, flip, shift)
+                name = f"dim {dim} flip {flip} shift {shift} t {t}"
+                y = timestep_embed_yardstick(t, 1, dim, flip, shift)
+                yield "timestep_embed", name, dict(ref=ref, A=A), y.to(dt)
+    for cfg in (False, True):
+        x, pred, coef = G.sched_inputs(SCHED_CPU_N, cfg, dt, seed_of("sched", cfg))
+        for step in range(coef.shape[0]):
+            ref, A = G.sched_step_ref(x, pred, cfg, 7.5, coef, step, 12345)
+            y = G.sched_step_ref(x, pred, cfg, 7.5, coef, step, 12345, torch.float32)[0]
+            # x' is an f32 output: the yardstick is judged in f32
+            yield "sched_step", f"cfg {cfg} step {step}", dict(ref=ref, A=A), y

@@ -180,6 +180,43 @@ def test_exact_flash_causal_pairing(cuda, dt, shape, pair_min):
         K.flash_set_pair_min(512)
 
 
+# Waves per workgroup of the 32x32x16 kernel.  The grids of FLASH_SHAPES are small, so auto
+# (the tests above) picks 1 or 2 waves at every entry; production shapes run 4.  An override
+# below the kernel's minimum (1 wave at D > 64) falls back to auto by design.
+FLASH_NW = [1, 2, 4]
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", X.FLASH_SHAPES)
+@pytest.mark.parametrize("nw", FLASH_NW)
+def test_exact_flash_attn_waves(cuda, dt, shape, nw):
+    """test_exact_flash_attn's cases (auto = nw 0 there) with 1, 2 and 4 waves forced: the
+    4-wave kernel, 128 query rows per workgroup, under the exact-arithmetic check."""
+    from cake_amd.ops import hip as K
+    K.flash_set_impl(2)
+    K.flash_set_nw(nw)
+    try:
+        _flash_run(shape, dt, f"nw {nw}")
+    finally:
+        K.flash_set_nw(0)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("shape", [s for s in X.FLASH_SHAPES if s[6]])
+@pytest.mark.parametrize("pair_min", [1, 0])
+@pytest.mark.parametrize("nw", FLASH_NW)
+def test_exact_flash_causal_pairing_waves(cuda, dt, shape, pair_min, nw):
+    """Causal q-tile pairing forced on and off at each tile size (32 nw query rows)."""
+    from cake_amd.ops import hip as K
+    K.flash_set_pair_min(pair_min)
+    K.flash_set_nw(nw)
+    try:
+        _flash_run(shape, dt, f"pair_min {pair_min} nw {nw}")
+    finally:
+        K.flash_set_nw(0)
+        K.flash_set_pair_min(512)
+
+
 @pytest.mark.parametrize("dt", DTYPES)
 @pytest.mark.parametrize("shape", X.FLASH_KSPLIT_SHAPES)
 @pytest.mark.parametrize("ksplit", [2, 4])

@@ -59,6 +59,7 @@ def _every_glue_case(dt):
                 ref, A = U.rope_ref(x, 2, hd, pos0, f)
                 yield "rope", f"hd {hd} T {T} pos0 {pos0}", dict(ref=ref, A=A), \
                     U.rope_ref(x, 2, hd, pos0, f, torch.float32)[0].to(dt)
+    yield from U.sd_glue_cases(dt)
 
 
 @pytest.mark.parametrize("dt", U.DTYPES, ids=DT_IDS)
