@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <list>
 #include <map>
 #include <memory>
@@ -48,6 +49,7 @@
 #include "../runtime/proto.h"
 #include "../runtime/safetensors.h"
 #include "engine_util.h"
+#include "llama_weights.h"
 
 namespace cake {
 namespace {
@@ -318,13 +320,13 @@ class Llama {
       lc_.V = vr.second - vr.first;
       if (lc_.I % 8 || (lc_.nh * cfg_.hd) % 8) throw Error("tensor-parallel slice not 8-aligned");
     }
-    if (wfmt_ == 1 && (cfg_.H % 16 || (cfg_.nh * cfg_.hd) % 16 || cfg_.I % 16))
-      throw Error("fp8 weights need hidden, attention and intermediate widths divisible by 16");
+    const FmtFacts& wf = fmt_facts(wfmt_);
+    if (cfg_.H % wf.multiple || (cfg_.nh * cfg_.hd) % wf.multiple || cfg_.I % wf.multiple)
+      throw Error(std::string(wf.name) + " weights need hidden, attention and intermediate "
+                  "widths divisible by " + std::to_string(wf.multiple));
     if (pfmt_ == 1 && (cfg_.H % 128 || (cfg_.nh * cfg_.hd) % 128 || cfg_.I % 128))
       throw Error("an fp8 MFMA prefill needs hidden, attention and intermediate widths divisible "
                   "by 128 (the k of one MFMA step)");
-    if (wfmt_ == 2 && (cfg_.H % 32 || (cfg_.nh * cfg_.hd) % 32 || cfg_.I % 32))
-      throw Error("mxfp4 weights need hidden, attention and intermediate widths divisible by 32");
     if (layers) {  // a TCP worker: the topology node's layers, no embedding / head
       hfmt_ = 0;   // no head here: the option is accepted and ignored
       owned_ = *layers;
@@ -369,9 +371,9 @@ class Llama {
       head_ = rank_ == 0;
       if (!head_) hfmt_ = 0;  // the head lives on rank 0: accepted and ignored elsewhere
     }
-    if (hfmt_ == 1 && cfg_.H % 16) throw Error("an fp8 lm_head needs a hidden width divisible by 16");
-    if (hfmt_ == 2 && cfg_.H % 32)
-      throw Error("an mxfp4 lm_head needs a hidden width divisible by 32");
+    if (const FmtFacts& hf = fmt_facts(hfmt_); cfg_.H % hf.multiple)
+      throw Error(std::string("an ") + hf.name + " lm_head needs a hidden width divisible by " +
+                  std::to_string(hf.multiple));
     lo_ = owned_.empty() ? 0 : owned_.front();
     hi_ = owned_.empty() ? 0 : owned_.back() + 1;
     local_.assign(cfg_.L, -1);
@@ -380,16 +382,14 @@ class Llama {
     planner_.load(pkg_dir() + "/ops/gemm_tuned.json");
     load_weights(dir);
     // one line per open: what the weights are and what they occupy
+    const std::string dtn = dt_ == 0 ? "bf16" : "f16";
     std::fprintf(stderr,
                  "cake engine: weights %s, lm_head %s, kv cache %s%s, %lld bytes on device (rank %d, "
                  "%d layers)\n",
-                 wfmt_ == 1 ? (dt_ == 0 ? "fp8 e4m3 projections (bf16 rest)"
-                                        : "fp8 e4m3 projections (f16 rest)")
-                 : wfmt_ == 2 ? (dt_ == 0 ? "mxfp4 projections (bf16 rest)"
-                                          : "mxfp4 projections (f16 rest)")
-                              : (dt_ == 0 ? "bf16" : "f16"),
-                 !head_ ? "none" : hfmt_ == 1 ? "fp8 e4m3" : hfmt_ == 2 ? "mxfp4"
-                                                : (dt_ == 0 ? "bf16" : "f16"),
+                 (wfmt_ == kFmt16 ? dtn
+                                  : fmt_facts(wfmt_).banner + (" projections (" + dtn + " rest)"))
+                     .c_str(),
+                 !head_ ? "none" : hfmt_ == kFmt16 ? dtn.c_str() : fmt_facts(hfmt_).banner,
                  kvfmt_ == kKvFp8 ? "fp8 e4m3"
                  : kvfmt_ == kKvFp8Emu ? (dt_ == 0 ? "fp8 e4m3 values in bf16 (test oracle)"
                                                    : "fp8 e4m3 values in f16 (test oracle)")
@@ -514,19 +514,7 @@ class Llama {
     k_check(cake_rmsnorm(dt_, hidden_, norm_, (float)cfg_.eps, n, H, x16_, st_), "rmsnorm");
     for (int v0 = 0; v0 < V; v0 += Vc) {
       const int w = std::min(Vc, V - v0);
-      const void* rows;
-      if (hfmt_ == 1) {
-        k_check(cake_dequant_rows_fp8(dt_, head_q_ + (size_t)v0 * H, head_s_ + v0, w, H, sc_head_,
-                                      st_), "dequant_rows_fp8 lm_head");
-        rows = sc_head_;
-      } else if (hfmt_ == 2) {
-        k_check(cake_dequant_rows_mxfp4(dt_, head_q_ + (size_t)v0 * H / 2,
-                                        head_e_ + (size_t)v0 * H / 32, w, H, sc_head_, st_),
-                "dequant_rows_mxfp4 lm_head");
-        rows = sc_head_;
-      } else {
-        rows = (const uint16_t*)lm_head_ + (size_t)v0 * H;
-      }
+      const void* rows = dense16(lm_head_, v0, w, sc_head_, dt_, st_);
       gemm(kEpiStore32, x16_, H, rows, H, nullptr, 0, sc_logits_, Vc, n, w, H, "gemm score head");
       k_check(cake_lse_rows(sc_logits_, Vc, n, w, v0, v0 == 0, sc_target_, sc_max_, sc_sum_,
                             sc_tgt_, sc_key_, st_), "lse_rows");
@@ -853,27 +841,16 @@ class Llama {
   }
 
  private:
-  struct P13Mat {  // one matrix packed by cake_pack13_rows: one allocation, three parts
-    uint8_t* planes = nullptr;
-    int* hdr = nullptr;
-    uint16_t* raw = nullptr;  // null: no raw rows
-    // the sub-matrix from row r0 on (q | k | v, gate | up: packed as one matrix)
-    const uint8_t* p(size_t r0, size_t K) const { return planes + r0 * (K / 8 * 13); }
-    const int* h(size_t r0) const { return hdr + r0; }
-  };
-  // weight_fmt 1: wqkv / wo / wgu / wd hold e4m3 codes, s* their f32 row scales (packed as
-  // the rows are: q|k|v, gate|up).  weight_fmt 2: they hold packed e2m1 codes [N, K/2], e*
-  // their e8m0 block-scale bytes [N, K/32] (packed the same way).
+  // One layer: the two norm vectors and its four projections, each a Mat (llama_weights.h) in
+  // the engine's weight_fmt: q | k | v rows and gate | up rows are one matrix each, and the
+  // GEMV dispatchers take the row blocks out of it.
   struct LayerW {
-    void *ln1, *wqkv, *wo, *ln2, *wgu, *wd;
-    float *sqkv = nullptr, *so = nullptr, *sgu = nullptr, *sd = nullptr;
-    uint8_t *eqkv = nullptr, *eo = nullptr, *egu = nullptr, *ed = nullptr;
-    P13Mat pqkv, po, pgu, pd;  // the packed twins decode reads (pack13_all); planes null: none
+    void *ln1 = nullptr, *ln2 = nullptr;
+    Mat qkv, o, gu, d;
   };
   // CAKE_PACK16 (docs/ENV.md): the lossless 13-bit copies of the bf16 projections and lm_head
-  // (kernels/gemv_p13_kernel.h) the decode GEMVs stream instead of the 16-bit rows, which
-  // stay resident for prefill, the f16 path, tensor parallelism and the oracles
-  P13Mat phead_;
+  // (kernels/gemv_p13_kernel.h; Mat::p13) the decode GEMVs stream instead of the 16-bit rows,
+  // which stay resident for prefill, the f16 path, tensor parallelism and the oracles
   int64_t packed_bytes_ = 0;
   int packed_mats_ = 0, packed_raw_rows_ = 0;
   bool pack_full_ = false;  // the HBM reserve was reached: the matrices after it stay 16-bit
@@ -905,11 +882,6 @@ class Llama {
   int pfmt_ = 0;
   uint16_t *kv16_k_ = nullptr, *kv16_v_ = nullptr;
   int64_t weight_bytes_ = 0;   // device weight allocations of this rank
-  // head_fmt 1: head_q_ holds the e4m3 codes [V, H], head_s_ the f32 row scales; head_fmt 2:
-  // head_q_ the packed e2m1 codes [V, H/2], head_e_ the e8m0 bytes [V, H/32].  lm_head_ is
-  // then null (untied) or the 16-bit embedding (tied: the gather needs it)
-  uint8_t *head_q_ = nullptr, *head_e_ = nullptr;
-  float* head_s_ = nullptr;
   // weight_fmt 1, 2: 16-bit scratch for the largest projection — the loader fills it before
   // each quantise (the 16-bit copy is never kept), prefill dequantises into it before
   // each GEMM
@@ -988,7 +960,11 @@ class Llama {
   int S_ = 0, k_ = 1;
   GemmPlanner planner_;
   std::vector<void*> allocs_;
-  void *embed_ = nullptr, *norm_ = nullptr, *lm_head_ = nullptr;
+  void *embed_ = nullptr, *norm_ = nullptr;
+  // the lm_head [V, H] in head_fmt (this rank's vocabulary rows under tensor parallelism).
+  // 16-bit with tied embeddings: embed_ itself; quantised: its own codes, tied or not, and
+  // embed_ stays for the gather.  Empty on a rank without the head.
+  Mat lm_head_;
   std::vector<LayerW> layers_;
   struct KV { uint8_t *k, *v; };            // [local layers][nkv][S][hd], kv_esize() bytes each
   std::map<uint64_t, KV> kv_;
@@ -1115,10 +1091,13 @@ class Llama {
     weight_bytes_ += (int64_t)n * 2;
     return dalloc<uint16_t>(n);
   }
-  // where the loader writes the 16-bit rows of a projection [N, K]: the tensor's own
-  // allocation, or (weight_fmt 1, 2) the shared scratch, sized for the largest projection
-  uint16_t* proj_stage(size_t N, size_t K) {
-    if (wfmt_ == 0) return walloc16(N * K);
+  // where the loader writes the 16-bit rows of an [N, K] matrix kept in format fmt: its own
+  // allocation (16-bit), the shared scratch sized for the largest projection (quantised), or
+  // with `temp` a buffer of its own (the [V, H] of a quantised untied head: not counted, keep()
+  // frees it before open returns, so an open peaks at the resident weights + 2 V H bytes)
+  uint16_t* stage(int fmt, size_t N, size_t K, bool temp = false) {
+    if (fmt == kFmt16) return walloc16(N * K);
+    if (temp) return dalloc<uint16_t>(N * K);
     if (!w16_) {
       const size_t H = cfg_.H, nq = (size_t)lc_.nh * cfg_.hd, nk = (size_t)lc_.nkv * cfg_.hd;
       const size_t I = lc_.I;
@@ -1126,75 +1105,80 @@ class Llama {
     }
     return w16_;
   }
-  // keep what proj_stage's buffer now holds: as it is, or quantised into its own codes +
-  // row scales (quant_fp8.hip) or codes + block-scale bytes (quant_mxfp4.hip); the scratch
-  // is free again on return
-  void proj_keep(uint16_t* staged, size_t N, size_t K, void*& w, float*& sc, uint8_t*& e8) {
-    if (wfmt_ == 0) {
-      w = staged;
-      return;
-    }
-    if (wfmt_ == 2) {
-      uint8_t* w4 = dalloc<uint8_t>(N * K / 2);
-      e8 = dalloc<uint8_t>(N * K / 32);
-      weight_bytes_ += (int64_t)(N * K / 2 + N * K / 32);
-      k_check(cake_quant_rows_mxfp4(dt_, staged, (int)N, (int)K, w4, e8, st_), "quant_rows_mxfp4");
-      hip_check(hipStreamSynchronize(st_), "sync");
-      w = w4;
-      return;
-    }
-    uint8_t* w8 = dalloc<uint8_t>(N * K);
-    sc = dalloc<float>(N);
-    weight_bytes_ += (int64_t)(N * K + 4 * N);
-    k_check(cake_quant_rows_fp8(dt_, staged, (int)N, (int)K, w8, sc, st_), "quant_rows_fp8");
+  // the matrix whose 16-bit rows `staged` holds: the rows as they are, or quantised into its
+  // own codes + side data (llama_weights.h quantise); the scratch is free again on return.
+  // `temp`: staged is stage()'s temporary and is freed (else the resident embedding)
+  Mat keep(int fmt, uint16_t* staged, size_t N, size_t K, bool temp = false) {
+    Mat m{fmt, N, K, staged};
+    if (fmt == kFmt16) return m;
+    m.w = dalloc<uint8_t>(fmt_code_bytes(fmt, N, K));
+    if (fmt == kFmtFp8) m.scale = dalloc<float>(N);
+    else m.e8 = dalloc<uint8_t>(fmt_side_bytes(fmt, N, K));
+    weight_bytes_ += (int64_t)m.bytes();
+    k_check(quantise(m, staged, dt_, st_), fmt == kFmtFp8 ? "quant_rows_fp8" : "quant_rows_mxfp4");
     hip_check(hipStreamSynchronize(st_), "sync");
-    w = w8;
-  }
-
-  // head_fmt 1, 2: the 16-bit rows of an untied head go through a temporary [V, H] buffer
-  // (not counted: head_keep frees it before open returns), so the peak of an open is the
-  // resident weights + 2 V H bytes
-  uint16_t* head_stage() {
-    if (hfmt_ == 0) return walloc16((size_t)lc_.V * cfg_.H);
-    return dalloc<uint16_t>((size_t)lc_.V * cfg_.H);
-  }
-  // keep the head rows16 holds: as they are, or quantised (the projections' row quantisers);
-  // `temp`: rows16 is head_stage's buffer and is freed, else it is the resident embedding
-  void head_keep(uint16_t* rows16, bool temp) {
-    if (hfmt_ == 0) {
-      lm_head_ = rows16;
-      return;
-    }
-    const size_t V = lc_.V, H = cfg_.H;
-    if (hfmt_ == 1) {
-      head_q_ = dalloc<uint8_t>(V * H);
-      head_s_ = dalloc<float>(V);
-      weight_bytes_ += (int64_t)(V * H + 4 * V);
-      k_check(cake_quant_rows_fp8(dt_, rows16, (int)V, (int)H, head_q_, head_s_, st_),
-              "quant_rows_fp8 lm_head");
-    } else {
-      head_q_ = dalloc<uint8_t>(V * H / 2);
-      head_e_ = dalloc<uint8_t>(V * H / 32);
-      weight_bytes_ += (int64_t)(V * H / 2 + V * H / 32);
-      k_check(cake_quant_rows_mxfp4(dt_, rows16, (int)V, (int)H, head_q_, head_e_, st_),
-              "quant_rows_mxfp4 lm_head");
-    }
-    hip_check(hipStreamSynchronize(st_), "sync");
-    if (temp) dfree(rows16);
-    else lm_head_ = rows16;
+    if (temp) dfree(staged);
+    return m;
   }
 
   // weights of this rank: all of the model, its pipeline layers, or (tensor parallel) its
   // slices — q / k / v rows of its heads, o_proj columns of its heads, gate / up rows and
   // down_proj columns of its intermediate range, lm_head rows of its vocabulary range
-  // (parallel/tensor_parallel.py shard_block / shard_head)
+  // (parallel/tensor_parallel.py shard_block / shard_head).  One list names a layer's tensors
+  // for both loaders, so a random_init engine has a checkpoint's shapes and packing.
+  struct Part { const char* name; size_t r0, nr, c0, nc; };  // a checkpoint tensor's slice
+  struct LayerTensor {
+    void* LayerW::*vec;  // a norm vector [N], or
+    Mat LayerW::*mat;    // a projection [N, K]: the parts' rows packed in order
+    size_t N, K;
+    uint64_t tag;  // random init: drawn whole (not per part) with tag 16 + 16 layer + tag
+    std::vector<Part> parts;
+  };
+  std::vector<LayerTensor> layer_tensors() const {
+    const size_t H = cfg_.H, hd = cfg_.hd, nq = lc_.nh * hd, nk = lc_.nkv * hd, I = lc_.I;
+    const size_t q0 = tp_rank_ * nq, k0 = tp_rank_ * nk, i0 = i0_;
+    return {
+        {&LayerW::ln1, nullptr, H, 1, 0, {{"input_layernorm.weight", 0, H, 0, 1}}},
+        {nullptr, &LayerW::qkv, nq + 2 * nk, H, 1,
+         {{"self_attn.q_proj.weight", q0, nq, 0, H},
+          {"self_attn.k_proj.weight", k0, nk, 0, H},
+          {"self_attn.v_proj.weight", k0, nk, 0, H}}},
+        {nullptr, &LayerW::o, H, nq, 2, {{"self_attn.o_proj.weight", 0, H, q0, nq}}},
+        {&LayerW::ln2, nullptr, H, 1, 3, {{"post_attention_layernorm.weight", 0, H, 0, 1}}},
+        {nullptr, &LayerW::gu, 2 * I, H, 4,
+         {{"mlp.gate_proj.weight", i0, I, 0, H}, {"mlp.up_proj.weight", i0, I, 0, H}}},
+        {nullptr, &LayerW::d, H, I, 5, {{"mlp.down_proj.weight", 0, H, i0, I}}},
+    };
+  }
+  // every owned layer's tensors: allocated (norms) or staged and kept (projections), their
+  // 16-bit values written by fill(layer, tensor, dst)
+  void load_layers(const std::function<void(int, const LayerTensor&, uint16_t*)>& fill) {
+    const std::vector<LayerTensor> tensors = layer_tensors();
+    layers_.resize(owned_.size());
+    for (int l : owned_) {
+      LayerW& w = layers_[local_[l]];
+      for (const LayerTensor& t : tensors) {
+        uint16_t* p = t.vec ? walloc16(t.N) : stage(wfmt_, t.N, t.K);
+        fill(l, t, p);
+        if (t.vec) w.*t.vec = p;
+        else w.*t.mat = keep(wfmt_, p, t.N, t.K);
+      }
+    }
+  }
+  // the lm_head of this rank's vocabulary rows: the embedding's rows when tied, else its own,
+  // written by fill(dst)
+  void load_head(bool tied, const std::function<void(uint16_t*)>& fill) {
+    const size_t V = lc_.V, H = cfg_.H;
+    uint16_t* p = tied ? static_cast<uint16_t*>(embed_) : stage(hfmt_, V, H, true);
+    if (!tied) fill(p);
+    lm_head_ = keep(hfmt_, p, V, H, !tied);
+  }
+
   // init = 1: this rank's tensors (same shapes and packing as a checkpoint load) drawn
   // on the device — N(0, 0.02) linears and lm_head, N(0, 1) embedding, N(1, 0.05) norms
   // (models/llama3/weights.py random) — keyed by (seed, layer, tensor)
   void load_random() {
-    const Cfg& c = cfg_;
-    const size_t H = c.H, V = c.V, hd = c.hd;
-    const size_t nq = (size_t)lc_.nh * hd, nk = (size_t)lc_.nkv * hd, I = lc_.I;
+    const size_t H = cfg_.H, V = cfg_.V;
     auto fill = [&](void* p, size_t n, float mean, float std, uint64_t tag) {
       const uint64_t key = seed_ * 0x9e3779b97f4a7c15ULL + tag * 0xc2b2ae3d27d4eb4fULL +
                            (uint64_t)tp_rank_ * 0x165667b19e3779f9ULL;
@@ -1205,33 +1189,12 @@ class Llama {
       fill(embed_, V * H, 0.f, 1.f, 1);
       norm_ = walloc16(H);
       fill(norm_, H, 1.f, 0.05f, 2);
-      if (c.tie && tp_ == 1) {
-        head_keep((uint16_t*)embed_, false);
-      } else {
-        uint16_t* hw = head_stage();  // the same draws whatever the head format
-        fill(hw, (size_t)lc_.V * H, 0.f, 0.02f, 3);
-        head_keep(hw, true);
-      }
+      load_head(cfg_.tie && tp_ == 1,  // (the same draws whatever the head format)
+                [&](uint16_t* hw) { fill(hw, (size_t)lc_.V * H, 0.f, 0.02f, 3); });
     }
-    layers_.resize(owned_.size());
-    for (int l : owned_) {
-      LayerW& w = layers_[local_[l]];
-      const uint64_t t = 16 + 16 * (uint64_t)l;
-      // a projection [N, K]: drawn as 16-bit rows, kept or quantised (proj_keep)
-      auto proj = [&](void*& wp, float*& sp, uint8_t*& ep, size_t N, size_t K, uint64_t tag) {
-        uint16_t* p = proj_stage(N, K);
-        fill(p, N * K, 0.f, 0.02f, tag);
-        proj_keep(p, N, K, wp, sp, ep);
-      };
-      w.ln1 = walloc16(H);
-      fill(w.ln1, H, 1.f, 0.05f, t);
-      proj(w.wqkv, w.sqkv, w.eqkv, nq + 2 * nk, H, t + 1);
-      proj(w.wo, w.so, w.eo, H, nq, t + 2);
-      w.ln2 = walloc16(H);
-      fill(w.ln2, H, 1.f, 0.05f, t + 3);
-      proj(w.wgu, w.sgu, w.egu, 2 * I, H, t + 4);
-      proj(w.wd, w.sd, w.ed, H, I, t + 5);
-    }
+    load_layers([&](int l, const LayerTensor& t, uint16_t* dst) {
+      fill(dst, t.N * t.K, t.vec ? 1.f : 0.f, t.vec ? 0.05f : 0.02f, 16 + 16 * (uint64_t)l + t.tag);
+    });
     hip_check(hipStreamSynchronize(st_), "sync");
   }
 
@@ -1241,11 +1204,7 @@ class Llama {
       return;
     }
     Checkpoint ck(dir);
-    const Cfg& c = cfg_;
-    const size_t H = c.H, V = c.V, hd = c.hd;
-    const size_t nq = (size_t)lc_.nh * hd, nk = (size_t)lc_.nkv * hd, I = lc_.I;
-    const size_t q0 = (size_t)tp_rank_ * lc_.nh * hd, k0 = (size_t)tp_rank_ * lc_.nkv * hd;
-    const size_t i0 = i0_;
+    const size_t H = cfg_.H, V = cfg_.V;
     void* stage = nullptr;
     size_t stage_bytes = 0;
     try {
@@ -1254,47 +1213,21 @@ class Llama {
         upload(ck, "model.embed_tokens.weight", embed_, V * H, stage, stage_bytes);
         norm_ = walloc16(H);
         upload(ck, "model.norm.weight", norm_, H, stage, stage_bytes);
-        const bool own_head = ck.has("lm_head.weight") && !c.tie;
+        const bool own_head = ck.has("lm_head.weight") && !cfg_.tie;
         const char* hn = own_head ? "lm_head.weight" : "model.embed_tokens.weight";
-        if (tp_ > 1) {
-          lm_head_ = walloc16((size_t)lc_.V * H);
-          upload_slice(ck, hn, lm_head_, voff_, lc_.V, 0, H, stage, stage_bytes);
-        } else if (own_head) {
-          uint16_t* hw = head_stage();
-          upload(ck, hn, hw, V * H, stage, stage_bytes);
-          head_keep(hw, true);
-        } else {
-          head_keep((uint16_t*)embed_, false);  // tied embeddings
-        }
+        load_head(tp_ == 1 && !own_head, [&](uint16_t* hw) {
+          if (tp_ > 1) upload_slice(ck, hn, hw, voff_, lc_.V, 0, H, stage, stage_bytes);
+          else upload(ck, hn, hw, V * H, stage, stage_bytes);
+        });
       }
-      layers_.resize(owned_.size());
-      for (int l : owned_) {
+      load_layers([&](int l, const LayerTensor& t, uint16_t* dst) {
         const std::string p = "model.layers." + std::to_string(l) + ".";
-        LayerW& w = layers_[local_[l]];
-        w.ln1 = walloc16(H);
-        upload(ck, p + "input_layernorm.weight", w.ln1, H, stage, stage_bytes);
-        // each projection: uploaded as 16-bit rows (its own allocation, or the shared
-        // scratch), then kept or quantised (proj_keep)
-        uint16_t* qkv = proj_stage(nq + 2 * nk, H);
-        upload_slice(ck, p + "self_attn.q_proj.weight", qkv, q0, nq, 0, H, stage, stage_bytes);
-        upload_slice(ck, p + "self_attn.k_proj.weight", qkv + nq * H, k0, nk, 0, H, stage,
-                     stage_bytes);
-        upload_slice(ck, p + "self_attn.v_proj.weight", qkv + (nq + nk) * H, k0, nk, 0, H, stage,
-                     stage_bytes);
-        proj_keep(qkv, nq + 2 * nk, H, w.wqkv, w.sqkv, w.eqkv);
-        uint16_t* wo = proj_stage(H, nq);
-        upload_slice(ck, p + "self_attn.o_proj.weight", wo, 0, H, q0, nq, stage, stage_bytes);
-        proj_keep(wo, H, nq, w.wo, w.so, w.eo);
-        w.ln2 = walloc16(H);
-        upload(ck, p + "post_attention_layernorm.weight", w.ln2, H, stage, stage_bytes);
-        uint16_t* gu = proj_stage(2 * I, H);
-        upload_slice(ck, p + "mlp.gate_proj.weight", gu, i0, I, 0, H, stage, stage_bytes);
-        upload_slice(ck, p + "mlp.up_proj.weight", gu + I * H, i0, I, 0, H, stage, stage_bytes);
-        proj_keep(gu, 2 * I, H, w.wgu, w.sgu, w.egu);
-        uint16_t* wd = proj_stage(H, I);
-        upload_slice(ck, p + "mlp.down_proj.weight", wd, 0, H, i0, I, stage, stage_bytes);
-        proj_keep(wd, H, I, w.wd, w.sd, w.ed);
-      }
+        if (t.vec) return upload(ck, p + t.parts[0].name, dst, t.N, stage, stage_bytes);
+        for (const Part& s : t.parts) {
+          upload_slice(ck, p + s.name, dst, s.r0, s.nr, s.c0, s.nc, stage, stage_bytes);
+          dst += s.nr * t.K;
+        }
+      });
     } catch (...) {
       if (stage) (void)hipFree(stage);
       throw;
@@ -1349,7 +1282,7 @@ class Llama {
     {
       const char* e = std::getenv("CAKE_ATTN_OPROJ");
       // (reads o_proj as 16-bit rows: off with fp8 and mxfp4 weights)
-      if (e && std::string(e) == "1" && wfmt_ == 0 && kvfmt_ == kKv16) ao_ = ao_fns();
+      if (e && std::string(e) == "1" && wfmt_ == kFmt16 && kvfmt_ == kKv16) ao_ = ao_fns();
       ao_ok_ = ao_.run != nullptr && ao_.supported(c.nh, c.nkv, c.hd, c.H) != 0;
     }
     // CAKE_ATTN_HEADS=<max keys>[:<waves>]: the head-parallel short-context attention
@@ -1383,15 +1316,16 @@ class Llama {
     hip_check(hipDeviceSynchronize(), "sync");  // null-stream memsets before st_ work
   }
 
-  // One matrix [N, K] of 16-bit rows -> its packed twin, if K is whole tiles and the copy
-  // fits above the HBM reserve (`required`: not fitting is an error).  kind: the row pairing
-  // of the GEMV that reads it (cake::PackKind: 0 adjacent rows, 1 head halves, 2 gate | up).
-  void pack13_one(int kind, const void* rows16, size_t N, size_t K, int hd, bool required,
-                  P13Mat& out) {
+  // One matrix of 16-bit rows gets its packed twin (m.p13), if K is whole tiles and the copy
+  // fits above the HBM reserve (`required`: not fitting is an error); a quantised or absent
+  // matrix has no rows to pack.  kind: the row pairing of the GEMV that reads it
+  // (cake::PackKind: 0 adjacent rows, 1 head halves, 2 gate | up).
+  void pack13_one(int kind, Mat& m, int hd, bool required) {
     constexpr size_t kReserve = (size_t)4 << 30;  // left free for sessions and library workspaces
-    if (pack_full_ || K % 2048 != 0) return;
-    const int nraw = cake_pack13_rows(kind, rows16, (int)N, (int)K, hd, nullptr, nullptr, nullptr,
-                                      0, st_);
+    const size_t N = m.N, K = m.K;
+    if (m.fmt != kFmt16 || !m.w || pack_full_ || K % 2048 != 0) return;
+    const int nraw = cake_pack13_rows(kind, m.w, (int)N, (int)K, hd, nullptr, nullptr, nullptr, 0,
+                                      st_);
     k_check(nraw < 0 ? -nraw : 0, "pack13_rows (count)");
     const size_t planes = N * (K / 8 * 13), hdrs = (N * 4 + 15) / 16 * 16;
     const size_t bytes = (size_t)cake_pack13_bytes((int)N, (int)K, nraw);
@@ -1407,14 +1341,14 @@ class Llama {
       return;
     }
     uint8_t* blk = dalloc<uint8_t>(bytes);
-    P13Mat m;
-    m.planes = blk;
-    m.hdr = reinterpret_cast<int*>(blk + planes);
-    m.raw = nraw ? reinterpret_cast<uint16_t*>(blk + planes + hdrs) : nullptr;
-    const int got = cake_pack13_rows(kind, rows16, (int)N, (int)K, hd, m.planes, m.hdr, m.raw,
-                                     nraw, st_);
+    P13Mat p;
+    p.planes = blk;
+    p.hdr = reinterpret_cast<int*>(blk + planes);
+    p.raw = nraw ? reinterpret_cast<uint16_t*>(blk + planes + hdrs) : nullptr;
+    const int got = cake_pack13_rows(kind, m.w, (int)N, (int)K, hd, p.planes, p.hdr, p.raw, nraw,
+                                     st_);
     k_check(got < 0 ? -got : (got == nraw ? 0 : (int)hipErrorUnknown), "pack13_rows");
-    out = m;
+    m.p13 = p;
     packed_bytes_ += (int64_t)bytes;
     packed_raw_rows_ += nraw;
     ++packed_mats_;
@@ -1437,18 +1371,16 @@ class Llama {
     }
     const char* ke = std::getenv("CAKE_PACK16_KINDS");
     const std::string kinds = "," + std::string(ke && *ke ? ke : kPack13Kinds) + ",";
-    auto on = [&](const char* k) { return kinds.find("," + std::string(k) + ",") != std::string::npos; };
-    const Cfg& c = lc_;
-    const size_t H = c.H, nq = (size_t)c.nh * c.hd, nk = (size_t)c.nkv * c.hd, I = c.I;
-    if (wfmt_ == 0)
-      for (LayerW& w : layers_) {
-        if (on("qkv")) pack13_one(1, w.wqkv, nq + 2 * nk, H, c.hd, required, w.pqkv);
-        if (on("o")) pack13_one(0, w.wo, H, nq, 0, required, w.po);
-        if (on("gu")) pack13_one(2, w.wgu, 2 * I, H, 0, required, w.pgu);
-        if (on("down")) pack13_one(0, w.wd, H, I, 0, required, w.pd);
-      }
-    if (head_ && hfmt_ == 0 && lm_head_ && on("head"))
-      pack13_one(0, lm_head_, (size_t)c.V, H, 0, required, phead_);
+    struct Entry { const char* name; int kind; Mat* m; int hd; };
+    auto pack = [&](std::initializer_list<Entry> entries) {
+      for (const Entry& x : entries)
+        if (kinds.find("," + std::string(x.name) + ",") != std::string::npos)
+          pack13_one(x.kind, *x.m, x.hd, required);
+    };
+    for (LayerW& w : layers_)
+      pack({{"qkv", 1, &w.qkv, lc_.hd}, {"o", 0, &w.o, 0}, {"gu", 2, &w.gu, 0},
+            {"down", 0, &w.d, 0}});
+    pack({{"head", 0, &lm_head_, 0}});
     std::fprintf(stderr,
                  "cake engine: decode streams %d matrices packed to 13 bits (%d raw rows), "
                  "%.2f GiB beside the 16-bit weights%s (rank %d)\n",
@@ -1582,7 +1514,7 @@ class Llama {
       const int t = std::max(T, sc_T_), v = std::max(Vc, sc_Vc_);
       dfree(sc_logits_);
       sc_logits_ = dalloc<float>((size_t)t * v);
-      if (hfmt_ != 0 && v > sc_Vc_) {
+      if (lm_head_.fmt != kFmt16 && v > sc_Vc_) {
         dfree(sc_head_);
         sc_head_ = dalloc<uint16_t>((size_t)v * cfg_.H);
       }
@@ -1738,33 +1670,24 @@ class Llama {
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
-      // weight_fmt 1, 2: each projection is dequantised into the 16-bit scratch right before
-      // its GEMM (one extra pass over the layer's weights per prefill; stream order keeps
-      // the four uses of the scratch apart)
-      auto w16 = [&](const void* wp, const float* sp, const uint8_t* ep, int N,
-                     int K) -> const void* {
-        if (wfmt_ == 0) return wp;
-        if (wfmt_ == 2)
-          k_check(cake_dequant_rows_mxfp4(dt_, wp, ep, N, K, w16_, st_), "dequant_rows_mxfp4");
-        else
-          k_check(cake_dequant_rows_fp8(dt_, wp, sp, N, K, w16_, st_), "dequant_rows_fp8");
-        return w16_;
-      };
-      // prefill_fmt 1: the activation rows quantised per token (the weights' own row
-      // quantiser over [T, K]), then the fp8 MFMA GEMM on the resident codes: no dequantise
-      // pass, the 16-bit scratch untouched
-      auto gemm8 = [&](int epi, const void* act, const void* wp, const float* sp, void* cptr,
-                       long long ldc, float* resid, long long ldr, int N, int K, const char* what) {
+      // one projection GEMM, act [T, K] . m^T.  prefill_fmt 1: the activation rows quantised
+      // per token (the weights' own row quantiser over [T, K]), then the fp8 MFMA GEMM on the
+      // resident codes: no dequantise pass, the 16-bit scratch untouched.  Else the 16-bit
+      // GEMM, on quantised weights (weight_fmt 1, 2) widened into the scratch right before it:
+      // one extra pass over the layer's weights per prefill; stream order keeps the four uses
+      // of the scratch apart
+      auto proj = [&](int epi, const void* act, const Mat& m, void* cptr, long long ldc,
+                      float* resid, long long ldr, int N, int K, const char* name) {
+        const std::string what = std::string(pfmt_ == 1 ? "gemm_w8a8 " : "gemm ") + name;
+        if (pfmt_ != 1)
+          return gemm(epi, act, K, dense16(m, 0, m.N, w16_, dt_, st_), K, cptr, ldc, resid, ldr, T,
+                      N, K, what.c_str());
         k_check(cake_quant_rows_fp8(dt_, act, T, K, a8_, sa_, st_), "quant_rows_fp8 (activations)");
-        k_check(cake_gemm_w8a8(dt_, epi, -1, a8_, K, sa_, wp, K, sp, cptr, ldc, resid, ldr, T, N, K,
-                               st_), what);
+        k_check(cake_gemm_w8a8(dt_, epi, -1, a8_, K, sa_, m.w, K, m.scale, cptr, ldc, resid, ldr, T,
+                               N, K, st_), what.c_str());
       };
       k_check(cake_rmsnorm(dt_, hidden_, w.ln1, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      if (pfmt_ == 1)
-        gemm8(kEpiStore, x16_, w.wqkv, w.sqkv, qkv_, nqkv, nullptr, 0, nqkv, c.H, "gemm_w8a8 qkv");
-      else
-        gemm(kEpiStore, x16_, c.H, w16(w.wqkv, w.sqkv, w.eqkv, nqkv, c.H), c.H, qkv_, nqkv, nullptr,
-             0, T, nqkv, c.H, "gemm qkv");
+      proj(kEpiStore, x16_, w.qkv, qkv_, nqkv, nullptr, 0, nqkv, c.H, "qkv");
       uint16_t* q = reinterpret_cast<uint16_t*>(qkv_);
       // (kv_fmt 0: cake_rope_kv itself)
       k_check(cake_rope_kv_kvf(dt_, q, q + nq, q + nq + nk, nqkv, nqkv, T, c.nh, c.nkv, c.hd,
@@ -1787,32 +1710,16 @@ class Llama {
                                      (long long)T * nq, c.hd, nq};
       k_check(cake_flash_attn(dt_, q, kr, vr, att_, 1, c.nh, c.nkv, T, Tk, c.hd, strides,
                               scale(), 1, pos0, st_), "flash_attn");
-      if (tp_ > 1) {  // partial o_proj over this rank's heads, summed over the ranks
-        gemm(kEpiStore32, att_, nq, w.wo, nq, nullptr, 0, ppart_, c.H, T, c.H, nq, "gemm o");
-        dense_allreduce(T);
-      } else if (pfmt_ == 1) {
-        gemm8(kEpiResid32, att_, w.wo, w.so, nullptr, 0, hidden_, c.H, c.H, nq, "gemm_w8a8 o");
-      } else {
-        gemm(kEpiResid32, att_, nq, w16(w.wo, w.so, w.eo, c.H, nq), nq, nullptr, 0, hidden_, c.H, T,
-             c.H, nq, "gemm o");
-      }
+      // tensor parallel: partial o_proj / down_proj over this rank's heads / intermediate
+      // range, summed over the ranks
+      float* const out = tp_ > 1 ? ppart_ : hidden_;
+      const int epi = tp_ > 1 ? kEpiStore32 : kEpiResid32;
+      proj(epi, att_, w.o, nullptr, 0, out, c.H, c.H, nq, "o");
+      if (tp_ > 1) dense_allreduce(T);
       k_check(cake_rmsnorm(dt_, hidden_, w.ln2, (float)c.eps, T, c.H, x16_, st_), "rmsnorm");
-      if (pfmt_ == 1)
-        gemm8(kEpiSwiglu, x16_, w.wgu, w.sgu, pact_, c.I, nullptr, 0, c.I, c.H,
-              "gemm_w8a8 gate|up");
-      else
-        gemm(kEpiSwiglu, x16_, c.H, w16(w.wgu, w.sgu, w.egu, 2 * c.I, c.H), c.H, pact_, c.I,
-             nullptr, 0, T, c.I, c.H, "gemm gate|up");
-      if (tp_ > 1) {
-        gemm(kEpiStore32, pact_, c.I, w.wd, c.I, nullptr, 0, ppart_, c.H, T, c.H, c.I, "gemm down");
-        dense_allreduce(T);
-      } else if (pfmt_ == 1) {
-        gemm8(kEpiResid32, pact_, w.wd, w.sd, nullptr, 0, hidden_, c.H, c.H, c.I,
-              "gemm_w8a8 down");
-      } else {
-        gemm(kEpiResid32, pact_, c.I, w16(w.wd, w.sd, w.ed, c.H, c.I), c.I, nullptr, 0, hidden_, c.H,
-             T, c.H, c.I, "gemm down");
-      }
+      proj(kEpiSwiglu, x16_, w.gu, pact_, c.I, nullptr, 0, c.I, c.H, "gate|up");
+      proj(epi, pact_, w.d, nullptr, 0, out, c.H, c.H, c.I, "down");
+      if (tp_ > 1) dense_allreduce(T);
     }
   }
 
@@ -1953,90 +1860,31 @@ class Llama {
                                part_, tickets_, attn_out_, st_), "attn_decode");
   }
 
+  // every GEMV through its dispatcher (llama_weights.h: the entry point of the matrix's format
+  // or packed twin); tensor parallel: o_proj / down_proj partial sums, summed over the ranks
   void step_layers(const std::vector<int>* sel = nullptr) {
     const Cfg& c = lc_;
-    const int nq = c.nh * c.hd, nk = c.nkv * c.hd;
+    const int nq = c.nh * c.hd;
     const int nl = sel ? (int)sel->size() : (int)layers_.size();
+    float* const out = tp_ > 1 ? partial_ : resid_;
+    const int accumulate = tp_ > 1 ? 0 : 1;
     for (int i = 0; i < nl; ++i) {
       const int l = sel ? (*sel)[i] : i;
       const LayerW& w = layers_[l];
-      if (wfmt_ == 2) {  // mxfp4 projections: the _w4 twins of the four GEMVs (tp_ == 1)
-        const uint8_t* q4 = reinterpret_cast<const uint8_t*>(w.wqkv);
-        const size_t rb = (size_t)c.H / 2, re = (size_t)c.H / 32;  // bytes per q|k|v row
-        k_check(cake_qkv_rope_w4_kvf(dt_, resid_, w.ln1, (float)c.eps, q4, q4 + (size_t)nq * rb,
-                                     q4 + (size_t)(nq + nk) * rb, w.eqkv, w.eqkv + (size_t)nq * re,
-                                     w.eqkv + (size_t)(nq + nk) * re, c.H, c.nh, c.nkv, c.hd,
-                                     inv_freq_, pos_, q_, kc(l), vc(l), S_, st_, kvfmt_),
-                "qkv_rope_w4");
-        attn(l);
-        k_check(cake_gemv_x16_w4(dt_, attn_out_, w.wo, w.eo, nq, c.H, resid_, 1, st_), "o_proj_w4");
-        const uint8_t* gu4 = reinterpret_cast<const uint8_t*>(w.wgu);
-        k_check(cake_swiglu_w4(dt_, resid_, w.ln2, (float)c.eps, gu4, gu4 + (size_t)c.I * rb,
-                               w.egu, w.egu + (size_t)c.I * re, c.H, c.I, act_, st_), "swiglu_w4");
-        k_check(cake_gemv_x16_w4(dt_, act_, w.wd, w.ed, c.I, c.H, resid_, 1, st_), "down_proj_w4");
-        continue;
-      }
-      if (wfmt_ == 1) {  // fp8 projections: the _w8 twins of the four GEMVs (tp_ == 1)
-        const uint8_t* q8 = reinterpret_cast<const uint8_t*>(w.wqkv);
-        k_check(cake_qkv_rope_w8_kvf(dt_, resid_, w.ln1, (float)c.eps, q8, q8 + (size_t)nq * c.H,
-                                     q8 + (size_t)(nq + nk) * c.H, w.sqkv, w.sqkv + nq,
-                                     w.sqkv + nq + nk, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
-                                     kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope_w8");
-        attn(l);
-        k_check(cake_gemv_x16_w8(dt_, attn_out_, w.wo, w.so, nq, c.H, resid_, 1, st_), "o_proj_w8");
-        const uint8_t* gu8 = reinterpret_cast<const uint8_t*>(w.wgu);
-        k_check(cake_swiglu_w8(dt_, resid_, w.ln2, (float)c.eps, gu8, gu8 + (size_t)c.I * c.H,
-                               w.sgu, w.sgu + c.I, c.H, c.I, act_, st_), "swiglu_w8");
-        k_check(cake_gemv_x16_w8(dt_, act_, w.wd, w.sd, c.I, c.H, resid_, 1, st_), "down_proj_w8");
-        continue;
-      }
-      // each 16-bit GEMV below runs its P13 twin when the matrix has a packed copy
-      // (pack13_all; tp_ == 1): bit-equal outputs from 13/16 of the bytes
-      const uint16_t* wqkv = reinterpret_cast<const uint16_t*>(w.wqkv);
-      if (const P13Mat& m = w.pqkv; m.planes)
-        k_check(cake_qkv_rope_p13_kvf(dt_, resid_, w.ln1, (float)c.eps, m.p(0, c.H), m.p(nq, c.H),
-                                      m.p(nq + nk, c.H), m.h(0), m.h(nq), m.h(nq + nk), m.raw,
-                                      m.raw, m.raw, c.H, c.nh, c.nkv, c.hd, inv_freq_, pos_, q_,
-                                      kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope_p13");
-      else
-        k_check(cake_qkv_rope_kvf(dt_, resid_, w.ln1, (float)c.eps, wqkv, wqkv + (size_t)nq * c.H,
-                                  wqkv + (size_t)(nq + nk) * c.H, c.H, c.nh, c.nkv, c.hd, inv_freq_,
-                                  pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope");
-      // one split: attention + o_proj in one launch
-      if (kvfmt_ != kKvFp8 && short_step_ && ao_ok_) {
-        k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.wo,
-                                nq, c.H, tp_ > 1 ? partial_ : resid_, tp_ > 1 ? 0 : 1, ao_ws_,
-                                ao_tickets_, tickets_ + 2 * c.nkv, st_), "attn_oproj");
-        if (tp_ > 1) ar_sum();
+      k_check(qkv_rope(dt_, resid_, w.ln1, (float)c.eps, w.qkv, c.H, c.nh, c.nkv, c.hd, inv_freq_,
+                       pos_, q_, kc(l), vc(l), S_, st_, kvfmt_), "qkv_rope", w.qkv);
+      if (kvfmt_ != kKvFp8 && short_step_ && ao_ok_) {  // one split: attention + o_proj fused
+        k_check(ao_.run(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(), w.o.w, nq, c.H,
+                        out, accumulate, ao_ws_, ao_tickets_, tickets_ + 2 * c.nkv, st_),
+                "attn_oproj");
       } else {  // (the fp8 cache runs with tp_ == 1)
         attn(l);
-        if (tp_ > 1) {
-          k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, partial_, 0, st_), "o_proj");
-          ar_sum();
-        } else if (w.po.planes) {
-          k_check(cake_gemv_x16_p13(dt_, attn_out_, w.po.planes, w.po.hdr, w.po.raw, nq, c.H,
-                                    resid_, 1, st_), "o_proj_p13");
-        } else {
-          k_check(cake_gemv_x16(dt_, attn_out_, w.wo, nq, c.H, resid_, 1, st_), "o_proj");
-        }
+        k_check(gemv_x16(dt_, attn_out_, w.o, nq, c.H, out, accumulate, st_), "o_proj", w.o);
       }
-      const uint16_t* wgu = reinterpret_cast<const uint16_t*>(w.wgu);
-      if (const P13Mat& m = w.pgu; m.planes)
-        k_check(cake_swiglu_p13(dt_, resid_, w.ln2, (float)c.eps, m.p(0, c.H), m.p(c.I, c.H),
-                                m.h(0), m.h(c.I), m.raw, m.raw, c.H, c.I, act_, st_),
-                "swiglu_p13");
-      else
-        k_check(cake_swiglu(dt_, resid_, w.ln2, (float)c.eps, wgu, wgu + (size_t)c.I * c.H, c.H,
-                            c.I, act_, st_), "swiglu");
-      if (tp_ > 1) {
-        k_check(cake_gemv_x16(dt_, act_, w.wd, c.I, c.H, partial_, 0, st_), "down_proj");
-        ar_sum();
-      } else if (w.pd.planes) {
-        k_check(cake_gemv_x16_p13(dt_, act_, w.pd.planes, w.pd.hdr, w.pd.raw, c.I, c.H, resid_, 1,
-                                  st_), "down_proj_p13");
-      } else {
-        k_check(cake_gemv_x16(dt_, act_, w.wd, c.I, c.H, resid_, 1, st_), "down_proj");
-      }
+      if (tp_ > 1) ar_sum();
+      k_check(swiglu(dt_, resid_, w.ln2, (float)c.eps, w.gu, c.H, c.I, act_, st_), "swiglu", w.gu);
+      k_check(gemv_x16(dt_, act_, w.d, c.I, c.H, out, accumulate, st_), "down_proj", w.d);
+      if (tp_ > 1) ar_sum();
     }
   }
 
@@ -2052,27 +1900,9 @@ class Llama {
     }
     if (m.fused) {
       const int last_n = m.penalty != 1.f ? m.last_n : 0;
-      if (hfmt_ == 1)
-        k_check(cake_head_select_w8(dt_, resid_, norm_, (float)c.eps, head_q_, head_s_, c.H, c.V,
-                                    logits_, hist_, hist_len_, last_n, m.penalty, slot_,
-                                    sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
-                "head_select_w8");
-      else if (hfmt_ == 2)
-        k_check(cake_head_select_w4(dt_, resid_, norm_, (float)c.eps, head_q_, head_e_, c.H, c.V,
-                                    logits_, hist_, hist_len_, last_n, m.penalty, slot_,
-                                    sel_ticket_, tok_, pos_, S_, embed_, resid_, st_),
-                "head_select_w4");
-      else if (phead_.planes)
-        k_check(cake_head_select_p13(dt_, resid_, norm_, (float)c.eps, phead_.planes, phead_.hdr,
-                                     phead_.raw, c.H, c.V, logits_, hist_, hist_len_, last_n,
-                                     m.penalty, slot_, sel_ticket_, tok_, pos_, S_, embed_, resid_,
-                                     st_),
-                "head_select_p13");
-      else
-        k_check(cake_head_select(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_,
-                                 hist_, hist_len_, last_n, m.penalty, slot_, sel_ticket_, tok_,
-                                 pos_, S_, embed_, resid_, st_),
-                "head_select");
+      k_check(head_select(dt_, resid_, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, hist_,
+                          hist_len_, last_n, m.penalty, slot_, sel_ticket_, tok_, pos_, S_, embed_,
+                          resid_, st_), "head_select", lm_head_);
       logprob_record(m);
       return;
     }
@@ -2081,21 +1911,11 @@ class Llama {
     logprob_record(m);
   }
 
-  // logits_ = lm_head . rms_norm(row): the 16-bit head or its quantised twin (head_fmt)
+  // logits_ = lm_head . rms_norm(row): the 16-bit head, its packed or its quantised twin
   void head_gemv(const float* row) {
     const Cfg& c = lc_;
-    if (hfmt_ == 1)
-      k_check(cake_gemv_norm_f32_w8(dt_, row, norm_, (float)c.eps, head_q_, head_s_, c.H, c.V,
-                                    logits_, st_), "lm_head_w8");
-    else if (hfmt_ == 2)
-      k_check(cake_gemv_norm_f32_w4(dt_, row, norm_, (float)c.eps, head_q_, head_e_, c.H, c.V,
-                                    logits_, st_), "lm_head_w4");
-    else if (phead_.planes)
-      k_check(cake_gemv_norm_f32_p13(dt_, row, norm_, (float)c.eps, phead_.planes, phead_.hdr,
-                                     phead_.raw, c.H, c.V, logits_, st_), "lm_head_p13");
-    else
-      k_check(cake_gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
-              "lm_head");
+    k_check(gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
+            "lm_head", lm_head_);
   }
 
   // f32 logits of the whole vocabulary for one hidden row: logits_ (one rank), or this
@@ -2686,8 +2506,7 @@ class Llama {
   // max over ranks; sampled: the full logits gathered, the single-GPU draw on each rank)
   void head_tp(const float* row, const Mode& m) {
     const Cfg& c = lc_;
-    k_check(cake_gemv_norm_f32(dt_, row, norm_, (float)c.eps, lm_head_, c.H, c.V, logits_, st_),
-            "lm_head");
+    head_gemv(row);
     if (m.greedy) {
       k_check(cake_select_shard(logits_, c.V, voff_, hist_, hist_len_, m.last_n, m.penalty, 0.f,
                                 0, slot_, st_), "select_shard");

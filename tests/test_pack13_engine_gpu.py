@@ -31,9 +31,9 @@ import json, sys
 import numpy as np
 from cake_amd.engine import NativeLlama, write_config
 from cake_amd.models.llama3.config import preset
-out, overrides, dtype = sys.argv[1], json.loads(sys.argv[2]), sys.argv[3]
+out, overrides, dtype, head = sys.argv[1], json.loads(sys.argv[2]), sys.argv[3], sys.argv[4]
 d = write_config(out + "/model", preset("tiny", **overrides))
-eng = NativeLlama(d, max_seq=256, dtype=dtype, random_init=True, seed=5)
+eng = NativeLlama(d, max_seq=256, dtype=dtype, random_init=True, seed=5, head=head)
 prompt = [1, 5, 7, 9, 11, 13, 17, 19]
 res = dict(packed=eng.packed_bytes(), weights=eng.weight_bytes())
 res["greedy"] = eng.generate(prompt, 48, repeat_penalty=1.1).tokens
@@ -45,7 +45,7 @@ print("RESULT " + json.dumps(res))
 """
 
 
-def _run(tmp_path, name, cfg, pack, dtype="bf16", kinds=None):
+def _run(tmp_path, name, cfg, pack, dtype="bf16", kinds=None, head="model"):
     out = tmp_path / name
     out.mkdir()
     env = {k: v for k, v in os.environ.items() if not k.startswith("CAKE_PACK16")}
@@ -54,7 +54,8 @@ def _run(tmp_path, name, cfg, pack, dtype="bf16", kinds=None):
     if kinds is not None:
         env["CAKE_PACK16_KINDS"] = kinds
     env["PYTHONPATH"] = str(ROOT) + os.pathsep + env.get("PYTHONPATH", "")
-    r = subprocess.run([sys.executable, "-c", CHILD, str(out), json.dumps(CONFIGS[cfg]), dtype],
+    r = subprocess.run([sys.executable, "-c", CHILD, str(out), json.dumps(CONFIGS[cfg]), dtype,
+                        head],
                        capture_output=True, text=True, env=env, timeout=300)
     if r.returncode != 0:
         return None, r.stderr
@@ -101,6 +102,26 @@ def test_every_kind_packed_equals_the_16_bit_engine(tmp_path):
     values = L * ((nq + 2 * nk) * H + H * nq + 3 * H * I) + V * H
     assert values * 13 // 8 <= every["packed"] < values * 2
     assert every["packed"] > dflt["packed"] >= L * 3 * H * I * 13 // 8
+
+
+@pytest.mark.parametrize("head", ["fp8", "mxfp4"])
+def test_packed_projections_with_a_quantised_head(tmp_path, head):
+    """Every projection packed beside a quantised lm_head: the head keeps its own format (it
+    has no 16-bit rows to pack) and the packed projections change no token and no logit bit."""
+    off, _ = _run(tmp_path, "off", "wide", "0", head=head)
+    every, log = _run(tmp_path, "all", "wide", "1", kinds=ALL_KINDS, head=head)
+    assert off is not None and every is not None, log
+    assert every["greedy"] == off["greedy"] and len(every["greedy"]) == 48
+    assert every["sampled"] == off["sampled"] and len(every["sampled"]) == 24
+    assert np.array_equal(every["forced"].view(np.int32), off["forced"].view(np.int32))
+    assert every["weights"] == off["weights"]
+    c = CONFIGS["wide"]
+    H, I, L = c["hidden_size"], c["intermediate_size"], c["num_hidden_layers"]
+    nq = c["num_attention_heads"] * 128
+    nk = c["num_key_value_heads"] * 128
+    values = L * ((nq + 2 * nk) * H + H * nq + 3 * H * I)  # without the head's V * H
+    assert values * 13 // 8 <= every["packed"] < values * 2
+    assert off["packed"] == 0
 
 
 def test_required_packing_refuses_f16(tmp_path):
