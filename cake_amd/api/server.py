@@ -13,7 +13,11 @@
   capitalised reference serialisation).  ``logprobs: true`` with ``top_logprobs`` in
   [0, 20] (the native engine) adds ``choices[0].logprobs.content``: one entry per
   emitted token, ``{token, id, logprob, bytes, top_logprobs: [{token, id, logprob,
-  bytes}]}``; a non-finite log-prob is sent as -9999.0.
+  bytes}]}``; a non-finite log-prob is sent as -9999.0.  ``presence_penalty`` /
+  ``frequency_penalty`` in [-2, 2], ``logit_bias`` (``{"<token id>": bias}``, at most 300
+  entries, bias in [-100, 100]) and ``min_p`` in [0, 1] (the native engine) act on the
+  logits before token selection (``engine.LogitControls``); absent or neutral values change
+  nothing, and a generator that cannot honour them answers 400 instead of ignoring them.
 * ``POST /api/v1/image`` — body ``{"image_args": {...sd-* keys...}}``,
   returns ``{"images": [base64 PNG, ...]}`` (image.rs:15-68).
 * anything else → 404 with body ``nope`` (mod.rs:19-21,40).
@@ -83,6 +87,37 @@ def request_logprobs(body: dict) -> int | None:
     return (top or 0) if want else None
 
 
+def request_logit_controls(body: dict, vocab_size: int | None = None):
+    """The request's ``engine.LogitControls`` (presence_penalty, frequency_penalty, logit_bias
+    in OpenAI's shape ``{"<token id>": bias}``, min_p), or None when every field is absent or
+    neutral.  ValueError on an invalid value."""
+    from ..engine import LogitControls
+    bias = body.get("logit_bias")
+    if bias is not None:
+        if not isinstance(bias, dict):
+            raise ValueError("logit_bias must be an object of token id -> bias")
+        ids = {}
+        for k, v in bias.items():
+            # OpenAI's keys are the ids as decimal strings
+            if not isinstance(k, str) or not k.isascii() or not k.isdigit():
+                raise ValueError(f"logit_bias keys must be token ids (non-negative integers), "
+                                 f"got {k!r}")
+            ids[int(k)] = v
+        if len(ids) != len(bias):
+            raise ValueError("logit_bias names a token id twice")
+        bias = ids
+
+    def field(name):
+        v = body.get(name)
+        return 0.0 if v is None else v
+
+    c = LogitControls(field("presence_penalty"), field("frequency_penalty"), bias,
+                      body.get("min_p"))
+    if vocab_size is not None:
+        c.check_vocab(vocab_size)
+    return None if c.neutral else c
+
+
 def logprob_entry(llm, tok) -> dict:
     """One ``logprobs.content`` entry of an emitted Token."""
     import math
@@ -140,6 +175,16 @@ def create_app(master):
             return JSONResponse({"error": "bad request: logprobs need the native engine (a "
                                           "GPU, f16 / bf16, graphs on, CAKE_NATIVE != 0)"},
                                 status_code=400)
+        try:
+            controls = request_logit_controls(
+                body, getattr(getattr(master.llm, "eng", None), "vocab_size", None))
+        except ValueError as e:
+            return JSONResponse({"error": f"bad request: {e}"}, status_code=400)
+        if controls is not None and not hasattr(master.llm, "set_logit_controls"):
+            return JSONResponse({"error": "bad request: presence_penalty, frequency_penalty, "
+                                          "logit_bias and min_p need the native engine (a GPU, "
+                                          "f16 / bf16, graphs on, CAKE_NATIVE != 0)"},
+                                status_code=400)
         model_name = master.llm.MODEL_NAME
         rid, created = str(uuid.uuid4()), int(time.time())
         role = "Assistant" if _reference_roles() else "assistant"
@@ -149,6 +194,8 @@ def create_app(master):
                 master.reset()
                 if hasattr(master.llm, "set_logprobs"):
                     master.llm.set_logprobs(want_lp)
+                if hasattr(master.llm, "set_logit_controls"):
+                    master.llm.set_logit_controls(controls)
                 # a new configuration, or an explicit seed (restart its stream)
                 if sampling is not None and (body.get("seed") is not None or
                                              sampling != getattr(master.llm, "sampling", None)):

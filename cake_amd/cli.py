@@ -117,6 +117,19 @@ def build_parser() -> argparse.ArgumentParser:
            "repeat penalty, before temperature / top-k / top-p); not with --parallel tp")
     a("--top-logprobs", type=int, default=None, metavar="K",
       help="with --logprobs-file: alternatives per token, 0..20 (0 when absent)")
+    a("--presence-penalty", type=float, default=None, metavar="F",
+      help="native Llama engine: F in [-2, 2] subtracted once from the logit of every token "
+           "this generation has already produced (after the repeat penalty; not with "
+           "--parallel tp)")
+    a("--frequency-penalty", type=float, default=None, metavar="F",
+      help="native Llama engine: F in [-2, 2] subtracted from such a token's logit once per "
+           "occurrence so far (not with --parallel tp)")
+    a("--min-p", type=float, default=None, metavar="F",
+      help="native Llama engine: sampled decoding keeps only tokens with p >= F * p_max, F in "
+           "(0, 1], together with --top-k / --top-p; greedy ignores it (not with --parallel tp)")
+    a("--logit-bias", default=None, metavar="ID:BIAS[,ID:BIAS...]",
+      help="native Llama engine: added to those tokens' logits, at most 300 distinct ids, BIAS "
+           "in [-100, 100] (not with --parallel tp)")
     a("--no-graph", action="store_true", help="disable hipGraph capture of the decode step")
     a("--trace", default=None, help="write a chrome-trace JSON of each text generation")
     a("--metrics", default=None, help="append one JSON line of stats per generation")
@@ -252,6 +265,67 @@ def logprobs_file_refusal(ctx) -> str | None:
     return None
 
 
+LOGIT_CONTROL_FLAGS = "--presence-penalty / --frequency-penalty / --min-p / --logit-bias"
+
+
+def parse_logit_bias(text: str) -> dict[int, float]:
+    """``ID:BIAS[,ID:BIAS...]`` -> ``{id: bias}``; ValueError on a malformed item or a repeated
+    id (ranges: ``engine.LogitControls``)."""
+    out: dict[int, float] = {}
+    for item in text.split(","):
+        tid, sep, val = item.partition(":")
+        if not sep or not tid.isascii() or not tid.isdigit():
+            raise ValueError(f"--logit-bias takes ID:BIAS[,ID:BIAS...], got {text!r}")
+        try:
+            b = float(val)
+        except ValueError:
+            raise ValueError(f"--logit-bias takes ID:BIAS[,ID:BIAS...], got {text!r}") from None
+        if int(tid) in out:
+            raise ValueError(f"--logit-bias names token id {int(tid)} twice")
+        out[int(tid)] = b
+    return out
+
+
+def cli_logit_controls(a):
+    """``engine.LogitControls`` of the four command-line flags, or None when none was given.
+    ValueError on a bad value."""
+    vals = [getattr(a, k, None) for k in ("presence_penalty", "frequency_penalty", "min_p",
+                                          "logit_bias")]
+    if all(v is None for v in vals):
+        return None
+    from .engine import LogitControls
+    pres, freq, min_p, bias = vals
+    return LogitControls(pres or 0.0, freq or 0.0, parse_logit_bias(bias) if bias else None,
+                         min_p)
+
+
+def logit_controls_refusal(ctx) -> str | None:
+    """Why this context cannot honour the logit-control flags (None: it can, or none was
+    given), in the wording of :func:`logprobs_file_refusal`: they are never silently ignored."""
+    a = ctx.args
+    try:
+        if cli_logit_controls(a) is None:
+            return None
+    except ValueError as e:
+        return str(e)
+    native = (f"{LOGIT_CONTROL_FLAGS} are served by the native Llama engine only (a GPU, --dtype "
+              "f16 or bf16, hipGraph decode, CAKE_NATIVE not 0)")
+    if ctx.model_type != "text-model":
+        return native + ": they apply to the text model only"
+    if a.transport == "rccl" and getattr(a, "parallel", "pp") == "tp":
+        return (f"{LOGIT_CONTROL_FLAGS} are not supported with --parallel tp: a tensor-parallel "
+                "engine shards the vocabulary")
+    if getattr(ctx, "score_file", None):
+        return f"{LOGIT_CONTROL_FLAGS} apply to generation, not to --score-file"
+    from .models.llama3.native_generator import native_eligible
+    if (not native_eligible(ctx) or a.transport != "tcp" or a.mode == "worker"
+            or getattr(a, "api", None)):
+        return native + ("; this run would take the Python path (or serve the API, whose requests "
+                         "carry their own values), which has no logit controls: refusing rather "
+                         "than generating without them")
+    return None
+
+
 def main(argv: list[str] | None = None) -> int:
     return _run(build_parser().parse_args(argv))
 
@@ -262,7 +336,7 @@ def _run(args) -> int:
     ctx = Context.from_args(args)
     why = (weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
            or prefill_dtype_refusal(ctx) or score_file_refusal(ctx)
-           or logprobs_file_refusal(ctx))
+           or logprobs_file_refusal(ctx) or logit_controls_refusal(ctx))
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2

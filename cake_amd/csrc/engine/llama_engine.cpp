@@ -578,6 +578,63 @@ class Llama {
     }
   }
 
+  // Logit controls of the generations that follow (null or all-neutral values: off).  Checked
+  // here; the count table [V], the parameter block and the state words are allocated at the
+  // first call that turns them on; the device block is written when a generation starts.
+  void set_logit_controls(const CakeLogitControls* c) {
+    LcSetting n;
+    if (c) {
+      auto in = [](float v, float lo, float hi) { return v >= lo && v <= hi; };  // NaN: false
+      if (!in(c->presence_penalty, -2.f, 2.f))
+        throw Error("logit controls: presence_penalty must lie in [-2, 2], got " +
+                    std::to_string(c->presence_penalty));
+      if (!in(c->frequency_penalty, -2.f, 2.f))
+        throw Error("logit controls: frequency_penalty must lie in [-2, 2], got " +
+                    std::to_string(c->frequency_penalty));
+      if (!in(c->min_p, 0.f, 1.f))
+        throw Error("logit controls: min_p must lie in [0, 1] (0: off), got " +
+                    std::to_string(c->min_p));
+      if (c->n_bias < 0 || c->n_bias > kLcMaxBias)
+        throw Error("logit controls: at most " + std::to_string(kLcMaxBias) +
+                    " logit_bias entries, got " + std::to_string(c->n_bias));
+      if (c->n_bias > 0 && (!c->bias_ids || !c->bias_values))
+        throw Error("logit controls: null logit_bias arrays");
+      n.ids.assign(c->bias_ids, c->bias_ids + c->n_bias);
+      n.vals.assign(c->bias_values, c->bias_values + c->n_bias);
+      std::vector<int32_t> sorted = n.ids;
+      std::sort(sorted.begin(), sorted.end());
+      for (int i = 0; i < c->n_bias; ++i) {
+        if (n.ids[i] < 0 || n.ids[i] >= cfg_.V)
+          throw Error("logit controls: logit_bias id " + std::to_string(n.ids[i]) +
+                      " is outside the vocabulary [0, " + std::to_string(cfg_.V) + ")");
+        if (i > 0 && sorted[i] == sorted[i - 1])
+          throw Error("logit controls: logit_bias id " + std::to_string(sorted[i]) +
+                      " is listed twice");
+        if (!in(n.vals[i], -100.f, 100.f))
+          throw Error("logit controls: logit_bias values must lie in [-100, 100], got " +
+                      std::to_string(n.vals[i]) + " for id " + std::to_string(n.ids[i]));
+      }
+      n.presence = c->presence_penalty;
+      n.frequency = c->frequency_penalty;
+      n.min_p = c->min_p;
+      n.on = n.presence != 0.f || n.frequency != 0.f || n.min_p > 0.f || c->n_bias > 0;
+    }
+    if (n.on && tp_ > 1)
+      throw Error("logit controls (presence_penalty, frequency_penalty, logit_bias, min_p) are "
+                  "not available on a tensor-parallel engine (the vocabulary is sharded)");
+    if (n.on && !head_)
+      throw Error("logit controls need an engine that holds the head (pipeline rank 0)");
+    if (n.on && !lc_cnt_) {
+      hip_check(hipSetDevice(dev_), "hipSetDevice");
+      lc_cnt_ = dalloc<unsigned int>((size_t)lc_.V);
+      lc_params_ = dalloc<unsigned int>(kLcParamWords);
+      lc_state_ = dalloc<unsigned int>(kLcStateWords);
+      hip_check(hipMemsetAsync(lc_state_, 0, sizeof(unsigned int) * kLcStateWords, st_), "memset");
+      hip_check(hipStreamSynchronize(st_), "sync");
+    }
+    lc_next_ = std::move(n);
+  }
+
   void generate(const int32_t* prompt, int T, int max_new, const CakeEngineSampling& smp,
                 const int32_t* eos, int n_eos, cake_engine_token_cb cb, void* ctx, int32_t* out,
                 int out_cap, CakeEngineStats* stats) {
@@ -771,6 +828,7 @@ class Llama {
     set_i32(pos_, T - 1);
     hip_check(hipMemsetAsync(slot_, 0, sizeof(unsigned long long), st_), "slot");
     Mode mode = mode_of(smp);
+    if (mode.controls) lc_begin(T, mode);
     // first token from the prefill logits (DeviceDecoder._select_first)
     if (tp_ > 1) {
       head_tp(hidden_ + (size_t)(T - 1) * cfg_.H, mode);
@@ -861,12 +919,22 @@ class Llama {
     int top_k = 0, last_n = 0;
     unsigned long long seed = 0;
     int logprobs = -1;  // >= 0: a log-prob record per token with that many alternatives
+    // logit controls: only on / off is part of the graphs; the values live in lc_params_
+    bool controls = false;  // the cake_logit_controls launch runs in select_tail
+    bool min_p = false;     // sampled, min_p on: its cut key joins the draw's threshold
     bool operator==(const Mode& o) const {
       return std::tie(fused, greedy, temperature, top_p, penalty, top_k, last_n, seed,
-                      logprobs) ==
+                      logprobs, controls, min_p) ==
              std::tie(o.fused, o.greedy, o.temperature, o.top_p, o.penalty, o.top_k, o.last_n,
-                      o.seed, o.logprobs);
+                      o.seed, o.logprobs, o.controls, o.min_p);
     }
+  };
+  // cake_engine_set_logit_controls, checked; on: some value is not neutral
+  struct LcSetting {
+    bool on = false;
+    float presence = 0.f, frequency = 0.f, min_p = 0.f;
+    std::vector<int32_t> ids;
+    std::vector<float> vals;
   };
 
   int dt_, dev_, init_ = 0;
@@ -1006,6 +1074,11 @@ class Llama {
   uint8_t* lp_ws_ = nullptr;
   unsigned int* lp_ticket_ = nullptr;
   std::vector<uint32_t> lp_host_;
+  // logit controls (set_logit_controls): the next generate()'s setting, the count table [V],
+  // the parameter block and the state words of kernels/logit_controls.hip
+  LcSetting lc_next_;
+  unsigned int *lc_cnt_ = nullptr, *lc_params_ = nullptr, *lc_state_ = nullptr;
+  std::vector<uint32_t> lc_host_;  // the block of the running generation (H2D source)
   float* ws_ = nullptr;
   size_t ws_n_ = 0;
   static constexpr size_t kLibWsBytes = 32u << 20;
@@ -1737,13 +1810,45 @@ class Llama {
     }
     m.fused = m.greedy && (m.penalty == 1.f || m.last_n <= kHeadSelectMaxLastN) && tp_ == 1;
     m.logprobs = lp_k_;
+    if (lc_next_.on) {  // the controls run in the unfused tail; greedy ignores min_p
+      m.min_p = !m.greedy && lc_next_.min_p > 0.f;
+      m.controls = m.min_p || lc_next_.presence != 0.f || lc_next_.frequency != 0.f ||
+                   !lc_next_.ids.empty();
+      if (m.controls) m.fused = false;
+    }
     return m;
   }
 
-  // logits -> penalty -> argmax / draw -> finalize (tok, history, pos)
+  // a generation with logit controls starts: the parameter block of lc_next_ (d = T ln min_p
+  // formed in f64, rounded once), an empty count table, counted = gen0 = the prompt length
+  void lc_begin(int n_prompt, const Mode& m) {
+    const LcSetting& c = lc_next_;
+    lc_host_.assign(kLcParamWords, 0u);
+    auto put = [&](int i, float v) { std::memcpy(&lc_host_[i], &v, 4); };
+    put(0, c.presence);
+    put(1, c.frequency);
+    put(2, m.min_p ? (float)((double)m.temperature * std::log((double)c.min_p)) : 0.f);
+    lc_host_[3] = (uint32_t)n_prompt;
+    lc_host_[4] = (uint32_t)c.ids.size();
+    lc_host_[5] = m.min_p ? 1u : 0u;
+    for (size_t i = 0; i < c.ids.size(); ++i) {
+      lc_host_[8 + i] = (uint32_t)c.ids[i];
+      put(8 + kLcMaxBias + (int)i, c.vals[i]);
+    }
+    hip_check(hipMemcpyAsync(lc_params_, lc_host_.data(), sizeof(uint32_t) * kLcParamWords,
+                             hipMemcpyHostToDevice, st_), "logit controls H2D");
+    hip_check(hipMemsetAsync(lc_cnt_, 0, sizeof(unsigned int) * (size_t)lc_.V, st_), "memset");
+    hip_check(hipMemsetAsync(lc_state_, 0, sizeof(unsigned int) * kLcStateWords, st_), "memset");
+    set_i32(reinterpret_cast<int*>(lc_state_ + 1), n_prompt);
+  }
+
+  // logits -> penalty -> logit controls -> argmax / draw -> finalize (tok, history, pos)
   void select_tail(const Mode& m) {
     if (m.penalty != 1.f)
       k_check(cake_repeat_penalty(logits_, hist_, hist_len_, m.last_n, m.penalty, st_), "penalty");
+    if (m.controls)  // counts hist_[counted, hist_len) first: before finalize moves hist_len
+      k_check(cake_logit_controls(logits_, lc_.V, hist_, hist_len_, lc_cnt_, lc_params_, lc_state_,
+                                  0, st_), "logit_controls");
     if (m.greedy) {
       k_check(cake_argmax(logits_, lc_.V, slot_, st_), "argmax");
     } else {
@@ -1751,8 +1856,13 @@ class Llama {
       if (restrict)
         k_check(cake_sample_threshold(logits_, lc_.V, m.temperature, m.top_k, m.top_p, thr_, st_),
                 "sample_threshold");
-      k_check(cake_gumbel_argmax(logits_, lc_.V, m.temperature, m.seed, hist_len_,
-                                 restrict ? thr_ : nullptr, slot_, st_), "gumbel_argmax");
+      const unsigned int* thr = restrict ? thr_ : nullptr;
+      if (m.min_p) {  // the sets intersect: the larger key
+        if (restrict) k_check(cake_logit_controls_merge_thr(thr_, lc_state_ + 2, st_), "merge_thr");
+        else thr = lc_state_ + 2;
+      }
+      k_check(cake_gumbel_argmax(logits_, lc_.V, m.temperature, m.seed, hist_len_, thr, slot_, st_),
+              "gumbel_argmax");
     }
     k_check(cake_finalize_token(slot_, tok_, hist_, hist_len_, pos_, S_, st_), "finalize");
   }
@@ -3153,6 +3263,18 @@ CAKE_API int32_t cake_engine_set_logprobs(void* h, int32_t top_k, char* err, int
   try {
     if (!h) throw cake::Error("null engine");
     static_cast<Llama*>(h)->set_logprobs(top_k);
+    return 0;
+  } catch (const std::exception& e) {
+    cake::put_err(err, errlen, e.what());
+    return 1;
+  }
+}
+
+CAKE_API int32_t cake_engine_set_logit_controls(void* h, const CakeLogitControls* c, char* err,
+                                                int32_t errlen) {
+  try {
+    if (!h) throw cake::Error("null engine");
+    static_cast<Llama*>(h)->set_logit_controls(c);
     return 0;
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());

@@ -121,6 +121,17 @@ struct CakeEngineSampling {
   int32_t repeat_last_n;
 };
 
+// Per-request logit controls (cake_engine_set_logit_controls): OpenAI's presence_penalty /
+// frequency_penalty / logit_bias and the min_p truncation rule.
+struct CakeLogitControls {
+  float presence_penalty;   // [-2, 2]; 0: off
+  float frequency_penalty;  // [-2, 2]; 0: off
+  float min_p;              // (0, 1]: on for sampled decoding; 0: off; greedy ignores it
+  int32_t n_bias;           // <= 300
+  const int32_t* bias_ids;  // [n_bias] distinct ids in [0, V)
+  const float* bias_values; // [n_bias] finite, in [-100, 100]
+};
+
 struct CakeEngineStats {
   int32_t n_prompt;
   int32_t n_generated;
@@ -217,6 +228,21 @@ int32_t cake_engine_set_logprobs(void* engine, int32_t top_k, char* err, int32_t
 int32_t cake_engine_logprobs(void* engine, int32_t first, int32_t count, int32_t* ids,
                              float* logit, float* lse, int32_t* top_ids, float* top_logits,
                              char* err, int32_t errlen);
+// Logit controls of the generations that follow (null: off, the default).  They act on the f32
+// row token selection sees, after the repeat penalty and before argmax / top-k / top-p / the
+// draw / the log-prob record, in one launch inside the decode step (kernels/logit_controls.hip):
+// with c[v] the occurrences of v among the tokens this generation has produced so far (the
+// prompt is not counted; a continue goes on counting), x[v] -= presence + frequency * c[v] where
+// c[v] > 0; then x[id] += b for every bias entry; then, for sampled decoding with min_p on, the
+// sampling set is cut to x[v] >= max x + T ln(min_p) and intersected with top-k / top-p.  Every
+// operation is one f32 rounding (ops/reference.py logit_controls_ref is bit-exact).  Takes
+// effect at the next cake_engine_generate; a continue keeps the setting of the generation it
+// continues.  All-neutral values (no penalty, no bias, min_p 0) are the same as null: the
+// default decode path.  Validated here: ranges, n_bias, distinct ids below V.  Refused: a
+// tensor-parallel engine, an engine without the head.  The count table and the parameter block
+// are allocated at the first call that turns the controls on.
+int32_t cake_engine_set_logit_controls(void* engine, const struct CakeLogitControls* c, char* err,
+                                       int32_t errlen);
 // "rank:first-last,..." layer runs of the token's walk (placement check); bytes written.
 int32_t cake_engine_walk(void* engine, char* out, int32_t cap);
 // Logits of the last prompt position after a prefill only (f32 [V] to host), for tests.

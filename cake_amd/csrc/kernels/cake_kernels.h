@@ -46,6 +46,9 @@ constexpr int kMaxSplit = 64;  // decode attention: splits per kv head (part: [n
 constexpr int kHeadSelectMaxLastN = 256;  // cake_head_select*: repeat-penalty window bound
 constexpr int kLpMaxK = 20;      // cake_logprob_topk: most alternatives per token
 constexpr int kLpRecWords = 48;  // cake_logprob_topk: 32-bit words per record (192 bytes)
+constexpr int kLcMaxBias = 300;     // cake_logit_controls: most logit_bias entries (OpenAI's limit)
+constexpr int kLcParamWords = 608;  // cake_logit_controls: 32-bit words of the parameter block
+constexpr int kLcStateWords = 68;   // cake_logit_controls: 32-bit words of the state block
 
 }  // namespace cake
 
@@ -301,6 +304,13 @@ int cake_bulk_send(const void* const* srcs, const unsigned long long* bytes,
                    hipStream_t st);
 int cake_bulk_recv(const void* rx, unsigned long long bytes, void* dst, unsigned int* seq,
                    int* err, double timeout_s, hipStream_t st);
+
+// ---- kernels/logit_controls.hip: count penalties, logit_bias and the min_p cut ---------
+// params: cake::kLcParamWords words, state: cake::kLcStateWords words, cnt: V words
+int cake_logit_controls(float* logits, int V, const int32_t* hist, const int32_t* hist_len,
+                        unsigned int* cnt, const void* params, unsigned int* state,
+                        int max_blocks, hipStream_t st);
+int cake_logit_controls_merge_thr(unsigned int* thr, const unsigned int* cut, hipStream_t st);
 
 // ---- kernels/logprob.hip: log-probs of a generated token -------------------------------
 long long cake_logprob_ws_bytes(int V);

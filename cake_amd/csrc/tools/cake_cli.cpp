@@ -12,6 +12,7 @@
 #include <dlfcn.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -130,6 +131,18 @@ const Flag kFlags[] = {
      "before temperature / top-k / top-p); not with --parallel tp"},
     {"--top-logprobs", "top_logprobs", PyArg::kInt, nullptr, nullptr, false,
      "with --logprobs-file: alternatives per token, 0..20 (0 when absent)"},
+    {"--presence-penalty", "presence_penalty", PyArg::kFloat, nullptr, nullptr, false,
+     "native Llama engine: F in [-2, 2] subtracted once from the logit of every token this "
+     "generation has already produced (after the repeat penalty; not with --parallel tp)"},
+    {"--frequency-penalty", "frequency_penalty", PyArg::kFloat, nullptr, nullptr, false,
+     "native Llama engine: F in [-2, 2] subtracted from such a token's logit once per "
+     "occurrence so far (not with --parallel tp)"},
+    {"--min-p", "min_p", PyArg::kFloat, nullptr, nullptr, false,
+     "native Llama engine: sampled decoding keeps only tokens with p >= F * p_max, F in (0, 1], "
+     "together with --top-k / --top-p; greedy ignores it (not with --parallel tp)"},
+    {"--logit-bias", "logit_bias", PyArg::kStr, nullptr, nullptr, false,
+     "native Llama engine: ID:BIAS[,ID:BIAS...] added to those tokens' logits, at most 300 "
+     "distinct ids, BIAS in [-100, 100] (not with --parallel tp)"},
     {"--no-graph", "no_graph", PyArg::kBool, "0", nullptr, true, "disable hipGraph decode"},
     {"--trace", "trace", PyArg::kStr, nullptr, nullptr, false, "chrome-trace JSON per generation"},
     {"--metrics", "metrics", PyArg::kStr, nullptr, nullptr, false, "append JSON stats lines"},
@@ -191,8 +204,61 @@ struct EngineApi {
   decltype(&cake_engine_score) score;
   decltype(&cake_engine_set_logprobs) set_logprobs;
   decltype(&cake_engine_logprobs) logprobs;
+  decltype(&cake_engine_set_logit_controls) set_logit_controls;
   decltype(&cake_engine_close) close;
 };
+
+// --presence-penalty / --frequency-penalty / --min-p / --logit-bias of the command line
+struct CliControls {
+  bool any = false;  // one of the four flags was given
+  float presence = 0.f, frequency = 0.f, min_p = 0.f;
+  std::vector<int32_t> ids;
+  std::vector<float> vals;
+};
+
+// Parses and range-checks the four flags; false with `why` set on a bad value.
+bool parse_controls(cake::PyArgs& o, CliControls* c, std::string* why) {
+  const auto range = [&](const char* dest, const char* flag, double lo, double hi, float* out) {
+    if (o[dest].kind == PyArg::kNone) return true;
+    c->any = true;
+    const double v = std::strtod(o[dest].value.c_str(), nullptr);
+    if (!(v >= lo && v <= hi)) {
+      *why = std::string(flag) + " must be in [" + std::to_string((int)lo) + ", " +
+             std::to_string((int)hi) + "], got " + o[dest].value;
+      return false;
+    }
+    *out = (float)v;
+    return true;
+  };
+  if (!range("presence_penalty", "--presence-penalty", -2, 2, &c->presence) ||
+      !range("frequency_penalty", "--frequency-penalty", -2, 2, &c->frequency) ||
+      !range("min_p", "--min-p", 0, 1, &c->min_p))
+    return false;
+  if (o["logit_bias"].kind == PyArg::kNone) return true;
+  c->any = true;
+  const std::string& s = o["logit_bias"].value;
+  const std::string bad = "--logit-bias takes ID:BIAS[,ID:BIAS...] (ID a token id, BIAS in "
+                          "[-100, 100], at most 300 distinct ids), got '" + s + "'";
+  size_t a = 0;
+  while (a <= s.size()) {
+    size_t b = s.find(',', a);
+    if (b == std::string::npos) b = s.size();
+    const std::string item = s.substr(a, b - a);
+    const size_t colon = item.find(':');
+    if (colon == std::string::npos || colon == 0 || colon + 1 >= item.size()) { *why = bad; return false; }
+    const std::string id = item.substr(0, colon), val = item.substr(colon + 1);
+    if (id.find_first_not_of("0123456789") != std::string::npos || id.size() > 9 ||
+        !valid_number(val, PyArg::kFloat)) { *why = bad; return false; }
+    const double v = std::strtod(val.c_str(), nullptr);
+    const int32_t tid = (int32_t)std::atoi(id.c_str());
+    if (!(v >= -100 && v <= 100) || std::find(c->ids.begin(), c->ids.end(), tid) != c->ids.end() ||
+        c->ids.size() >= 300) { *why = bad; return false; }
+    c->ids.push_back(tid);
+    c->vals.push_back((float)v);
+    a = b + 1;
+  }
+  return true;
+}
 
 bool native_text_eligible(cake::PyArgs& o, bool text, bool worker, bool has_topology) {
   const char* env = std::getenv("CAKE_NATIVE");
@@ -296,6 +362,23 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
                          "tensor-parallel engine shards the vocabulary\n");
     return 2;
   }
+  CliControls lc;
+  std::string lc_why;
+  if (!parse_controls(o, &lc, &lc_why)) {  // main() checked already: unreachable
+    std::fprintf(stderr, "cake-cli: %s\n", lc_why.c_str());
+    return 2;
+  }
+  if (lc.any && o["transport"].value == "rccl" && o["parallel"].value == "tp") {
+    std::fprintf(stderr, "cake-cli: --presence-penalty / --frequency-penalty / --min-p / "
+                         "--logit-bias are not supported with --parallel tp: a tensor-parallel "
+                         "engine shards the vocabulary\n");
+    return 2;
+  }
+  if (lc.any && scoring) {
+    std::fprintf(stderr, "cake-cli: --presence-penalty / --frequency-penalty / --min-p / "
+                         "--logit-bias apply to generation, not to --score-file\n");
+    return 2;
+  }
   const std::string lib = cake::package_root() + "/cake_amd/lib/libcake_engine.so";
   void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!h) {
@@ -314,8 +397,11 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   api.set_logprobs =
       reinterpret_cast<decltype(api.set_logprobs)>(dlsym(h, "cake_engine_set_logprobs"));
   api.logprobs = reinterpret_cast<decltype(api.logprobs)>(dlsym(h, "cake_engine_logprobs"));
+  api.set_logit_controls = reinterpret_cast<decltype(api.set_logit_controls)>(
+      dlsym(h, "cake_engine_set_logit_controls"));
   if (!api.open || !api.generate || !api.close || !api.open_pp || !api.serve || !api.open_tp ||
-      !api.open_remote || !api.score || !api.set_logprobs || !api.logprobs) {
+      !api.open_remote || !api.score || !api.set_logprobs || !api.logprobs ||
+      !api.set_logit_controls) {
     std::fprintf(stderr, "cake-cli: engine symbols missing in %s\n", lib.c_str());
     return 1;
   }
@@ -494,6 +580,15 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   const int32_t max_new = n < room ? n : room;
   std::vector<int32_t> out((size_t)(max_new > 0 ? max_new : 1));
   CakeEngineStats st{};
+  if (lc.any) {
+    const CakeLogitControls c{lc.presence, lc.frequency, lc.min_p, (int32_t)lc.ids.size(),
+                              lc.ids.data(), lc.vals.data()};
+    if (api.set_logit_controls(eng, &c, err, sizeof(err))) {
+      std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
+      api.close(eng);
+      return 1;
+    }
+  }
   std::FILE* lp_file = nullptr;
   if (lp_on) {
     if (api.set_logprobs(eng, lp_k, err, sizeof(err))) {
@@ -666,6 +761,14 @@ int main(int argc, char** argv) {
     const long long k = std::strtoll(opts["top_logprobs"].value.c_str(), nullptr, 10);
     if (k < 0 || k > 20) {
       std::fprintf(stderr, "cake-cli: --top-logprobs must be in [0, 20], got %lld\n", k);
+      return 2;
+    }
+  }
+  {  // the logit-control flags' own values, before anything starts
+    CliControls lc;
+    std::string why;
+    if (!parse_controls(opts, &lc, &why)) {
+      std::fprintf(stderr, "cake-cli: %s\n", why.c_str());
       return 2;
     }
   }

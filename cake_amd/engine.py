@@ -132,6 +132,8 @@ def _bind(L) -> None:
     L.cake_engine_set_logprobs.restype = I
     L.cake_engine_logprobs.argtypes = [P, I, I, IP, FP, FP, IP, FP, C.c_char_p, I]
     L.cake_engine_logprobs.restype = I
+    L.cake_engine_set_logit_controls.argtypes = [P, C.POINTER(LogitControls), C.c_char_p, I]
+    L.cake_engine_set_logit_controls.restype = I
     L.cake_engine_close.argtypes = [P]
     L.cake_engine_close.restype = None
 
@@ -160,6 +162,94 @@ class GenResult:
 
 
 LOGPROBS_MAX_TOP = 20
+LOGIT_BIAS_MAX = 300   # OpenAI's limit on logit_bias entries
+NO_LOGIT_CONTROLS_TP = ("logit controls (presence_penalty, frequency_penalty, logit_bias, min_p) "
+                        "are not available on a tensor-parallel engine (the vocabulary is "
+                        "sharded)")
+
+
+class LogitControls(C.Structure):
+    """Per-request controls on the f32 row token selection sees, after the repeat penalty and
+    before argmax / top-k / top-p / the draw / the log-prob record (OpenAI's fields and min_p);
+    also the ctypes mirror of ``struct CakeLogitControls``:
+
+    * ``presence_penalty`` / ``frequency_penalty`` in [-2, 2]: with ``c[v]`` the occurrences of
+      v among the tokens this generation has produced so far (the prompt is not counted),
+      ``x[v] -= presence + frequency * c[v]`` where ``c[v] > 0``;
+    * ``logit_bias``: ``{id: bias}``, at most 300 distinct ids, each bias finite in
+      [-100, 100]: ``x[id] += bias``, after the penalty;
+    * ``min_p`` in (0, 1] (None or 0: off): with ``temperature > 0`` the sampling set is cut to
+      ``x[v] >= max x + T ln(min_p)`` (p[v] >= min_p p_max) and intersected with top-k / top-p;
+      greedy decoding ignores it.
+
+    The constructor checks the values (``ValueError``) and keeps them as f32, the engine's
+    type; ``neutral`` is true when nothing would change a token."""
+    _fields_ = [("presence_penalty", C.c_float), ("frequency_penalty", C.c_float),
+                ("min_p", C.c_float), ("n_bias", C.c_int32),
+                ("bias_ids", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float))]
+
+    def __init__(self, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 logit_bias: "dict[int, float] | None" = None, min_p: "float | None" = None):
+        import math
+
+        def num(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) \
+                    or not lo <= v <= hi:
+                raise ValueError(f"{name}: a number in [{lo}, {hi}], got {v!r}")
+            return float(v)
+
+        bias: dict[int, float] = {}
+        if logit_bias is not None:
+            if not isinstance(logit_bias, dict):
+                raise ValueError("logit_bias: a mapping of token id to bias, "
+                                 f"got {type(logit_bias).__name__}")
+            if len(logit_bias) > LOGIT_BIAS_MAX:
+                raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries, "
+                                 f"got {len(logit_bias)}")
+            for k, v in logit_bias.items():
+                if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < 2 ** 31:
+                    raise ValueError("logit_bias: token ids are non-negative integers, "
+                                     f"got {k!r}")
+                bias[k] = num(f"logit_bias[{k}]", v, -100, 100)
+        self._ids = (C.c_int32 * max(1, len(bias)))(*bias.keys())      # kept alive with self
+        self._vals = (C.c_float * max(1, len(bias)))(*bias.values())
+        super().__init__(num("presence_penalty", presence_penalty, -2, 2),
+                         num("frequency_penalty", frequency_penalty, -2, 2),
+                         0.0 if min_p is None else num("min_p", min_p, 0, 1), len(bias),
+                         C.cast(self._ids, C.POINTER(C.c_int32)),
+                         C.cast(self._vals, C.POINTER(C.c_float)))
+
+    @property
+    def logit_bias(self) -> "dict[int, float]":
+        return {int(self._ids[i]): float(self._vals[i]) for i in range(self.n_bias)}
+
+    @property
+    def neutral(self) -> bool:
+        return (self.presence_penalty == 0 and self.frequency_penalty == 0 and self.min_p == 0
+                and self.n_bias == 0)
+
+    def _key(self):
+        return (self.presence_penalty, self.frequency_penalty, self.min_p,
+                tuple(self.logit_bias.items()))
+
+    def __eq__(self, other):
+        return isinstance(other, LogitControls) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return (f"LogitControls(presence_penalty={self.presence_penalty!r}, frequency_penalty="
+                f"{self.frequency_penalty!r}, logit_bias={self.logit_bias!r}, "
+                f"min_p={self.min_p or None!r})")
+
+    def check_vocab(self, vocab_size: int) -> "LogitControls":
+        """``ValueError`` if a bias id is not below ``vocab_size``; returns self."""
+        for k in self.logit_bias:
+            if k >= vocab_size:
+                raise ValueError(f"logit_bias: token id {k} is outside the vocabulary "
+                                 f"[0, {vocab_size})")
+        return self
 
 
 @dataclass
@@ -284,6 +374,7 @@ class NativeLlama:
             raise ValueError(f"native engine prefill: one of {sorted(PREFILL_FORMATS)}, "
                              f"got {prefill!r}")
         self.prefill = prefill
+        self.tp = bool(tp and world > 1)
         self.weights = weights
         self.head = head
         self.kv = kv
@@ -454,11 +545,19 @@ class NativeLlama:
                  repeat_penalty: float = 1.1, repeat_last_n: int = 128,
                  eos_ids: list[int] | None = None,
                  on_token: Callable[[int], bool | None] | None = None,
-                 logprobs: int | None = None) -> GenResult:
+                 logprobs: int | None = None, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0, logit_bias: dict[int, float] | None = None,
+                 min_p: float | None = None) -> GenResult:
         """``logprobs``: None = off; K in [0, 20] = a log-prob record per generated token with
         the K most likely alternatives (:class:`TokenLogprobs` in ``GenResult.logprobs``; inside
         ``on_token``, :meth:`token_logprob`).  The tokens are the same either way.  Not with
-        ``tp=True`` nor on a ``layers`` engine."""
+        ``tp=True`` nor on a ``layers`` engine.
+        ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` / ``min_p``: the
+        :class:`LogitControls` of this generation (and of the calls of :meth:`continue_` after
+        it); all neutral = the default decode path.  The log-prob records see the row after the
+        penalties and the bias.  Not with ``tp=True`` nor on a ``layers`` engine."""
+        self.set_logit_controls(LogitControls(presence_penalty, frequency_penalty, logit_bias,
+                                              min_p))
         self.set_logprobs(logprobs)
         arr = (C.c_int32 * len(prompt))(*prompt)
         smp = EngineSampling(float(temperature or 0.0), int(top_k or 0), float(top_p or 0.0),
@@ -479,6 +578,24 @@ class NativeLlama:
         if lib().cake_engine_set_logprobs(self._h, want, err, len(err)):
             raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
         self._lp_next = want
+
+    def set_logit_controls(self, c: LogitControls | None) -> None:
+        """The :class:`LogitControls` of the next :meth:`generate` (None or all neutral: off).
+        The values were checked when ``c`` was built and its ids are checked against the
+        vocabulary here, before the library is touched (``ValueError``); the engine refuses
+        controls on a tensor-parallel engine and on one without the head (``RuntimeError``)."""
+        c = c or LogitControls()
+        if not c.neutral and getattr(self, "tp", False):  # the engine's own refusal, before
+            raise RuntimeError("native engine: " + NO_LOGIT_CONTROLS_TP)  # any library call
+        c.check_vocab(self.vocab_size)
+        if c == getattr(self, "_lc_next", LogitControls()):
+            return
+        err = C.create_string_buffer(1024)
+        rc = lib().cake_engine_set_logit_controls(self._h, None if c.neutral else C.byref(c), err,
+                                                  len(err))
+        if rc:
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        self._lc_next = c
 
     def _logprobs(self, first: int, count: int) -> TokenLogprobs:
         import numpy as np

@@ -50,6 +50,10 @@ class Master:
             lp_path = getattr(a, "logprobs_file", None)
             if lp_path:  # cli.logprobs_file_refusal let only the native engine through
                 self.llm.set_logprobs(int(getattr(a, "top_logprobs", None) or 0))
+            from .cli import cli_logit_controls
+            controls = cli_logit_controls(a)
+            if controls is not None:  # cli.logit_controls_refusal let only the native engine through
+                self.llm.set_logit_controls(controls)
             self.generate_text(out)
             sys.stdout.write("\n")
             if lp_path:

@@ -36,6 +36,7 @@ class NativeLLM(TextGenerator):
         self.last_stats = None
         self.last_result = None
         self.logprobs: int | None = None   # set_logprobs
+        self.logit_controls = None         # set_logit_controls (engine.LogitControls)
 
     # ------------------------------------------------------------------ factory
     @classmethod
@@ -85,6 +86,13 @@ class NativeLLM(TextGenerator):
         self.eng.set_logprobs(k)
         self.logprobs = None if k is None else int(k)
 
+    def set_logit_controls(self, c) -> None:
+        """presence_penalty / frequency_penalty / logit_bias / min_p (``engine.LogitControls``)
+        from the next generation on; None or all neutral = off.  ``ValueError`` for a bad
+        value; refused by a tensor-parallel engine."""
+        self.eng.set_logit_controls(c)
+        self.logit_controls = None if c is None or c.neutral else c
+
     def latency_ms(self) -> tuple[float, float] | None:
         """(p50, p99) device time per decode token of the last generation."""
         r = self.last_result
@@ -115,9 +123,14 @@ class NativeLLM(TextGenerator):
 
     def _kw(self) -> dict:
         s = self.sampling
-        return dict(temperature=0.0 if s.greedy else float(s.temperature),
-                    top_k=s.top_k, top_p=s.top_p, seed=int(s.seed),
-                    repeat_penalty=float(s.repeat_penalty), repeat_last_n=int(s.repeat_last_n))
+        kw = dict(temperature=0.0 if s.greedy else float(s.temperature),
+                  top_k=s.top_k, top_p=s.top_p, seed=int(s.seed),
+                  repeat_penalty=float(s.repeat_penalty), repeat_last_n=int(s.repeat_last_n))
+        c = self.logit_controls
+        if c is not None:
+            kw.update(presence_penalty=c.presence_penalty, frequency_penalty=c.frequency_penalty,
+                      logit_bias=c.logit_bias, min_p=c.min_p)
+        return kw
 
     def _prompt(self) -> list[int]:
         return self.tokenizer.encode(self.history.encode_dialog_to_prompt(),

@@ -152,6 +152,9 @@ _SIGS = {
     "cake_hop_recv": (I, [P, I, I, I, P, P, P, D, P]),
     "cake_bulk_send": (I, [P, P, P, I, P, U, P, P, P]),
     "cake_bulk_recv": (I, [P, U, P, P, P, D, P]),
+    # kernels/logit_controls.hip: count penalties, logit_bias and the min_p cut
+    "cake_logit_controls": (I, [P, I, P, P, P, P, P, I, P]),
+    "cake_logit_controls_merge_thr": (I, [P, P, P]),
     # kernels/logprob.hip: log-probs of a generated token
     "cake_logprob_ws_bytes": (L, [I]),
     "cake_logprob_topk": (I, [P, I, P, P, I, P, I, P, P, I, P]),

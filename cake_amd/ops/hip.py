@@ -1791,3 +1791,65 @@ def logprob_topk(logits, tok, hist_len, k: int, rec, ws, ticket, max_blocks: int
     check(kernels().cake_logprob_topk(_p(logits), V, _p(tok), _p(hist_len), int(k), _p(rec),
                                       rec.shape[0], _p(ws), _p(ticket), int(max_blocks),
                                       _stream()), "logprob_topk")
+
+
+LOGIT_BIAS_MAX = 300            # entries of a logit_bias list
+LOGIT_CONTROLS_PARAM_WORDS = 608  # int32 words of the parameter block
+LOGIT_CONTROLS_STATE_WORDS = 68   # int32 words of the state block
+
+
+def pack_logit_controls(presence: float, frequency: float, bias, min_p: float | None,
+                        temperature: float, gen0: int) -> torch.Tensor:
+    """Host int32 [608] parameter block of :func:`logit_controls`: presence | frequency |
+    d = float32(T ln min_p) | gen0 | n_bias | min_p on | 2 zero words | 300 ids | 300 values.
+    min_p is on only with temperature > 0 and 0 < min_p <= 1 (greedy ignores it)."""
+    import numpy as np
+
+    from .reference import min_p_offset
+    items = list(bias.items()) if hasattr(bias, "items") else list(bias or [])
+    if len(items) > LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_bias: at most {LOGIT_BIAS_MAX} entries, got {len(items)}")
+    on = temperature > 0 and min_p is not None and 0 < min_p <= 1
+    w = np.zeros(LOGIT_CONTROLS_PARAM_WORDS, dtype=np.int32)
+    f = w.view(np.float32)
+    f[0], f[1] = presence, frequency
+    f[2] = min_p_offset(temperature, min_p) if on else 0.0
+    w[3], w[4], w[5] = int(gen0), len(items), int(on)
+    for e, (i, b) in enumerate(items):
+        w[8 + e] = int(i)
+        f[8 + LOGIT_BIAS_MAX + e] = float(b)
+    return torch.from_numpy(w)
+
+
+def logit_controls(logits, hist, hist_len, cnt, params, state, max_blocks: int = 0):
+    """One pass of the count penalties, the bias list and the min_p cut over `logits` (f32 [V],
+    any 4-byte aligned view, adjusted in place): see logit_controls.hip and
+    :func:`cake_amd.ops.reference.logit_controls_ref`.  hist (int32) / hist_len (int32[1]): the
+    device history; cnt: int32 [V], the count table, which the launch brings up to the histogram
+    of hist[gen0, hist_len); params: int32 [608] (:func:`pack_logit_controls`, on the device);
+    state: int32 [68], zeroed once: 0 ticket (left zero) | 1 counted | 2 cut key (0: no
+    restriction) | 3 key of the adjusted row's maximum | 4.. scratch.  A generation starts with
+    cnt zeroed and state[1] = gen0."""
+    if logits.dim() != 1 or logits.dtype != torch.float32 or not logits.is_cuda or (
+            logits.numel() > 1 and logits.stride(0) != 1):
+        raise ValueError("logit_controls: logits must be a device float32 [V] view of unit stride")
+    V = logits.numel()
+    if V < 1:
+        raise ValueError("logit_controls: empty row")
+    _req(hist, "hist", dtype=torch.int32)
+    _req(hist_len, "hist_len", dtype=torch.int32, numel=1)
+    _req(cnt, "cnt", dtype=torch.int32, numel=V)
+    _req(params, "params", dtype=torch.int32, numel=LOGIT_CONTROLS_PARAM_WORDS)
+    _req(state, "state", dtype=torch.int32, numel=LOGIT_CONTROLS_STATE_WORDS)
+    check(kernels().cake_logit_controls(_p(logits), V, _p(hist), _p(hist_len), _p(cnt),
+                                        _p(params), _p(state), int(max_blocks), _stream()),
+          "logit_controls")
+
+
+def logit_controls_merge_thr(thr, cut):
+    """thr[0] = max(thr[0], cut[0]) as unsigned keys: the min_p cut key merged into the top-k /
+    top-p threshold of :func:`sample_threshold`."""
+    _req(thr, "thr", dtype=torch.int32, numel=1)
+    _req(cut, "cut", dtype=torch.int32, numel=1)
+    check(kernels().cake_logit_controls_merge_thr(_p(thr), _p(cut), _stream()),
+          "logit_controls_merge_thr")

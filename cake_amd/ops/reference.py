@@ -222,3 +222,64 @@ def logprob_topk_ref(x_f32: torch.Tensor, tok: int, k: int) -> dict:
     logit = x[int(tok)].clone()
     return {"id": int(tok), "logit": logit, "lse": lse, "logprob": float(lp(logit)),
             "top_ids": top_ids, "top_logits": top_logits, "top_logprobs": lp(top_logits)}
+
+
+LOGIT_BIAS_MAX = 300  # OpenAI's limit on logit_bias entries
+
+
+def ordered_key(x) -> "np.ndarray":
+    """The order-preserving u32 key of sampling.hip for float32 values (numpy uint32)."""
+    import numpy as np
+    u = np.asarray(x, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def min_p_offset(temperature: float, min_p: float) -> float:
+    """``d = float32(T * ln(min_p))``: formed in float64 and rounded once."""
+    import numpy as np
+    return float(np.float32(float(temperature) * math.log(float(min_p))))
+
+
+def logit_controls_ref(x, generated, presence: float = 0.0, frequency: float = 0.0, bias=None,
+                       min_p: float | None = None, temperature: float = 0.0):
+    """Oracle of logit_controls.hip for one row: ``(x_adj, cut_key | None)``.
+
+    ``x`` is the f32 row after the repeat penalty; ``generated`` the tokens this generation has
+    produced so far (the prompt is not counted); ``bias`` a mapping or a sequence of pairs
+    ``id -> b`` with distinct ids.  In numpy float32, every operation rounded on its own:
+
+    1. ``c[v]`` = occurrences of v in ``generated``; for ``c[v] > 0``:
+       ``x[v] = x[v] - (presence + frequency * float32(c[v]))`` (skipped when both are zero);
+    2. ``x[id] = x[id] + b`` for every bias entry, after the penalty;
+    3. with ``temperature > 0`` and ``0 < min_p <= 1``: ``cut = max(x) + d``,
+       ``d = float32(T ln min_p)``, and the sampling set is
+       ``ordered(x[v]) >= cut_key = min(ordered(cut), ordered(max))`` (the second term only
+       matters for a maximum of -0.0 with d = 0, whose sum is +0.0).  Otherwise ``None``.
+
+    Returns ``x_adj`` as a float32 CPU tensor and the key as an int.  NaN logits are outside the
+    contract."""
+    import numpy as np
+    if isinstance(x, torch.Tensor):
+        x = x.detach().reshape(-1).to(torch.float32).cpu().numpy()
+    x = np.array(x, dtype=np.float32).reshape(-1)
+    V = x.size
+    pres, freq = np.float32(presence), np.float32(frequency)
+    if pres != 0 or freq != 0:
+        c = np.bincount(np.asarray([t for t in generated if 0 <= int(t) < V], dtype=np.int64),
+                        minlength=V)
+        hit = c > 0
+        pen = pres + freq * c[hit].astype(np.float32)  # float32 product, then float32 sum
+        x[hit] = x[hit] - pen.astype(np.float32)
+    items = list(bias.items()) if hasattr(bias, "items") else list(bias or [])
+    if len(items) > LOGIT_BIAS_MAX or len({int(i) for i, _ in items}) != len(items):
+        raise ValueError("bias: at most 300 entries with distinct ids")
+    for i, b in items:
+        x[int(i)] = x[int(i)] + np.float32(b)
+    cut_key = None
+    if temperature > 0 and min_p is not None and 0 < min_p <= 1:
+        keys = ordered_key(x)
+        kmax = keys.max()
+        xmax = x[int(keys.argmax())]
+        cut = np.float32(xmax + np.float32(min_p_offset(temperature, min_p)))
+        cut_key = int(min(int(ordered_key(cut)), int(kmax)))
+    return torch.from_numpy(x), cut_key
