@@ -14,8 +14,7 @@
 #include <utility>
 #include <vector>
 
-#include "../runtime/json.h"
-#include "../runtime/net.h"
+#include "../runtime/star.h"
 
 namespace cake {
 
@@ -34,7 +33,7 @@ inline void k_check(int rc, const char* what) {
 }
 
 // ---------------------------------------------------------------------------
-// control plane of the multi-rank engines: IPC handles as hex, JSON frames over TCP
+// IPC handles as hex, for the hellos of the multi-rank control plane (runtime/star.h)
 // ---------------------------------------------------------------------------
 inline std::string hex_of(const void* p, size_t n) {
   static const char* d = "0123456789abcdef";
@@ -54,11 +53,19 @@ inline void unhex(const std::string& s, void* out, size_t n) {
   for (size_t i = 0; i < n; ++i) b[i] = (uint8_t)(v(s[2 * i]) << 4 | v(s[2 * i + 1]));
 }
 
-inline void send_json(int fd, const Json& j) {
-  const std::string t = j.dump();
-  send_frame(fd, reinterpret_cast<const uint8_t*>(t.data()), (uint32_t)t.size());
+inline std::string ipc_export(void* p) {
+  hipIpcMemHandle_t h;
+  hip_check(hipIpcGetMemHandle(&h, p), "IpcGetMemHandle");
+  return hex_of(&h, sizeof(h));
 }
-inline Json recv_json(int fd) { return Json::parse(recv_frame(fd)); }
+
+inline void* ipc_import(const std::string& hex, const char* what) {
+  hipIpcMemHandle_t h;
+  unhex(hex, &h, sizeof(h));
+  void* p = nullptr;
+  hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), what);
+  return p;
+}
 
 // <root>/cake_amd/lib/libcake_engine.so -> <root>/cake_amd
 inline std::string pkg_dir() {

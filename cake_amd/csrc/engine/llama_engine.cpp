@@ -23,7 +23,6 @@
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <chrono>
@@ -428,14 +427,13 @@ class Llama {
     (void)hipSetDevice(dev_);
     (void)hipStreamSynchronize(st_);
     if (rank_ == 0 && tp_rank_ == 0)
-      for (int fd : peers_) {
+      for (int r = 1; r <= ctl_.workers(); ++r) {
         try {
-          send_json(fd, msg("exit"));
+          ctl_.send(r, msg("exit"));
         } catch (const std::exception&) {
         }
       }
-    for (int fd : peers_) tcp_close(fd);
-    if (ctl_fd_ >= 0) tcp_close(ctl_fd_);
+    ctl_.close();
     for (auto& r : remotes_)
       if (r.fd >= 0) tcp_close(r.fd);
     drop_graphs();
@@ -528,7 +526,7 @@ class Llama {
     hip_check(hipMemcpyAsync(topv, sc_topv_, sizeof(float) * n, hipMemcpyDeviceToHost, st_),
               "D2H");
     hip_check(hipStreamSynchronize(st_), "sync");
-    if (world_ > 1) sync_workers();
+    if (world_ > 1) sync_workers(hop_drain());
     check_attn_error("rank " + std::to_string(rank()));
   }
 
@@ -658,7 +656,7 @@ class Llama {
       m.set("penalty", Json::number(smp.repeat_penalty));
       m.set("last_n", Json::integer(smp.repeat_last_n));
       m.set("eos", eos_json(eos, n_eos));
-      for (int fd : peers_) send_json(fd, m);
+      ctl_.broadcast(m);
     }
     run_generation(prompt, T, max_new, smp, eos, n_eos, cb, ctx, out, out_cap, stats, true);
   }
@@ -679,7 +677,7 @@ class Llama {
       Json m = msg("continue");
       m.set("max_new", Json::integer(max_new));
       m.set("eos", eos_json(eos, n_eos));
-      for (int fd : peers_) send_json(fd, m);
+      ctl_.broadcast(m);
     }
     lp_begin(last_mode_.logprobs >= 0, max_new);
     const auto t0 = std::chrono::steady_clock::now();
@@ -784,8 +782,8 @@ class Llama {
     const int rc = cake_graph_decode(&spec, &res);
     trace(rank(), "decode loop done: " + std::to_string(res.n_tokens) + " tokens, " +
                       std::to_string(res.replays) + " replays, rc " + std::to_string(rc));
-    if (world_ > 1) sync_workers();
-    if (tp_ > 1 && lead) sync_tp_workers();
+    if (world_ > 1) sync_workers(hop_drain());
+    if (tp_ > 1 && lead) sync_workers(ar_drain());
     k_check(rc, "graph_decode");
     if (lead) check_attn_error("rank " + std::to_string(rank()));  // TP workers: in "sync"
     int n_out = 0;
@@ -1003,7 +1001,7 @@ class Llama {
   float* relay_ = nullptr;
   unsigned int* seq_ = nullptr;
   int* hop_err_ = nullptr;
-  std::vector<int> peers_;  // rank 0: control sockets of ranks 1..world-1
+  Star ctl_;  // control sockets of the pipeline or tensor-parallel ranks, rank 0 the hub
   // tensor parallel
   struct ArChan {
     void* inbox = nullptr;
@@ -1022,7 +1020,6 @@ class Llama {
   unsigned int* ar_seq_ = nullptr;
   int* ar_err_ = nullptr;
   std::vector<void*> peer_slab_, tp_mapped_, tp_owned_;
-  int ctl_fd_ = -1;         // workers: control socket to rank 0
   hipStream_t st_ = nullptr;
   Cfg cfg_;
   int S_ = 0, k_ = 1;
@@ -1702,8 +1699,8 @@ class Llama {
       m.set("T", Json::integer(T));
       m.set("stop", Json::integer((int64_t)i));
       trace(rank_, "prefill stop " + std::to_string(i) + " -> rank " + std::to_string(s.rank));
-      send_json(peers_[s.rank - 1], m);
-      const Json ack = recv_json(peers_[s.rank - 1]);
+      ctl_.send(s.rank, m);
+      const Json ack = ctl_.recv(s.rank);
       if (!ack.has("ok") || !ack.get("ok").as_bool())
         throw Error("pipeline rank " + std::to_string(s.rank) + " prefill failed: " +
                     (ack.has("error") ? ack.get("error").as_string() : std::string("?")));
@@ -2055,7 +2052,7 @@ class Llama {
       for (int i = 0; i < n; ++i) fr.push(Json::integer(forced[i]));
       m.set("prompt", pr);
       m.set("forced", fr);
-      for (int fd : peers_) send_json(fd, m);
+      ctl_.broadcast(m);
     }
     prefill_body(prompt, T);
     const size_t V = cfg_.V;
@@ -2067,12 +2064,11 @@ class Llama {
     forced_ = true;
     try {
       for (int i = 0; i < n; ++i) {
-        if (world_ > 1)
-          for (int fd : peers_) {
-            Json st = msg("fstep");
-            st.set("pos", Json::integer(T + i));
-            send_json(fd, st);
-          }
+        if (world_ > 1) {
+          Json st = msg("fstep");
+          st.set("pos", Json::integer(T + i));
+          ctl_.broadcast(st);
+        }
         set_i32(tok_, forced[i]);
         set_i32(pos_, T + i);
         short_step_ = short_at(T + i);
@@ -2089,8 +2085,8 @@ class Llama {
       throw;
     }
     forced_ = false;
-    if (world_ > 1) sync_workers();
-    if (tp_ > 1 && lead) sync_tp_workers();
+    if (world_ > 1) sync_workers(hop_drain());
+    if (tp_ > 1 && lead) sync_workers(ar_drain());
     if (lead) check_attn_error("rank " + std::to_string(rank()));
   }
 
@@ -2263,35 +2259,67 @@ class Llama {
       Json m = msg("replays");
       m.set("count", Json::integer(count));
       m.set("pos", Json::integer(a->pos0 + (int64_t)first * a->self->k_));
-      for (int fd : a->self->peers_) send_json(fd, m);
+      a->self->ctl_.broadcast(m);
       return 0;
     } catch (const std::exception&) {
       return 1;
     }
   }
 
-  // every worker drained its stream; any hop that gave up waiting is an error
-  void sync_workers() {
+  // The device-side waits of a mode and how its drain names them: the error words a wait
+  // that gave up sets, their key in a worker's "sync" reply, and the texts.
+  struct Drain {
+    int* err;
+    int words;
+    const char *key, *label, *what;
+  };
+  Drain hop_drain() const {
+    return {hop_err_, 1, "hop_err", "pipeline rank ", "hop receive timed out"};
+  }
+  Drain ar_drain() const {
+    return {ar_err_, 3, "ar_err", "tensor-parallel rank ", "all-reduce timed out"};
+  }
+
+  // this rank's error words, read and reset (a worker reports what it can: unchecked)
+  static int take_errors(const Drain& d, bool checked) {
+    int w[3] = {0, 0, 0};
+    const hipError_t e = hipMemcpy(w, d.err, sizeof(int) * d.words, hipMemcpyDeviceToHost);
+    if (checked) hip_check(e, d.key);
+    if (w[0] | w[1] | w[2]) (void)hipMemset(d.err, 0, sizeof(int) * d.words);
+    return w[0] | w[1] | w[2];
+  }
+
+  // rank 0: every worker drained its stream; any wait that gave up is an error
+  void sync_workers(const Drain& d) {
     std::string err;
-    for (size_t i = 0; i < peers_.size(); ++i) {
+    for (int r = 1; r <= ctl_.workers(); ++r) {
       try {
-        send_json(peers_[i], msg("sync"));
-        const Json r = recv_json(peers_[i]);
-        if (r.has("hop_err") && r.get("hop_err").as_int() != 0)
-          err = "pipeline rank " + std::to_string(i + 1) + ": hop receive timed out";
-        if (r.has("error")) err = "pipeline rank " + std::to_string(i + 1) + ": " +
-                                  r.get("error").as_string();
+        ctl_.send(r, msg("sync"));
+        const Json j = ctl_.recv(r);
+        const std::string who = d.label + std::to_string(r) + ": ";
+        if (j.has(d.key) && j.get(d.key).as_int() != 0) err = who + d.what;
+        if (j.has("error")) err = (tp_ > 1 ? "" : who) + j.get("error").as_string();
       } catch (const std::exception& e) {
         err = e.what();
       }
     }
-    int own = 0;
-    hip_check(hipMemcpy(&own, hop_err_, sizeof(int), hipMemcpyDeviceToHost), "hop_err");
-    if (own) {
-      (void)hipMemset(hop_err_, 0, sizeof(int));
-      err = "pipeline rank 0: hop receive timed out";
-    }
+    if (take_errors(d, true)) err =std::string(d.label) + "0: " + d.what;
     if (!err.empty()) throw Error(err);
+  }
+
+  // a worker's answer to "sync": its stream drained, its error words, what went wrong
+  void reply_sync(const Drain& d) {
+    Json r = Json::object();
+    const hipError_t e = hipStreamSynchronize(st_);
+    r.set("ok", Json::boolean(e == hipSuccess));
+    r.set(d.key, Json::integer(take_errors(d, false)));
+    if (e != hipSuccess) r.set("error", Json::string(hipGetErrorString(e)));
+    try {  // pipeline: rank 0 names the rank before whatever this reports
+      check_attn_error(tp_ > 1 ? d.label + std::to_string(tp_rank_) : "attention");
+    } catch (const std::exception& x) {
+      r.set("error", Json::string(x.what()));
+    }
+    ctl_.send(0, r);
   }
 
  public:
@@ -2308,7 +2336,7 @@ class Llama {
     if (active) ensure_graphs(Mode{});
     std::vector<void*> execs(execs_.begin(), execs_.end());
     for (;;) {
-      const Json m = recv_json(ctl_fd_);
+      const Json m = ctl_.recv(0);
       const std::string cmd = m.get("cmd").as_string();
       trace(rank_, "control: " + m.dump().substr(0, 120));
       if (cmd == "exit") break;
@@ -2328,7 +2356,7 @@ class Llama {
           r.set("ok", Json::boolean(false));
           r.set("error", Json::string(e.what()));
         }
-        send_json(ctl_fd_, r);
+        ctl_.send(0, r);
       } else if (cmd == "fstep") {  // one eager teacher-forced step of this rank's stops
         if (!active) continue;
         Mode fm;
@@ -2350,20 +2378,7 @@ class Llama {
         CakeLoopResult res{};
         k_check(cake_graph_decode(&spec, &res), "graph_decode");  // enqueue only
       } else if (cmd == "sync") {
-        Json r = Json::object();
-        const hipError_t e = hipStreamSynchronize(st_);
-        int herr = 0;
-        (void)hipMemcpy(&herr, hop_err_, sizeof(int), hipMemcpyDeviceToHost);
-        if (herr) (void)hipMemset(hop_err_, 0, sizeof(int));
-        r.set("ok", Json::boolean(e == hipSuccess));
-        r.set("hop_err", Json::integer(herr));
-        if (e != hipSuccess) r.set("error", Json::string(hipGetErrorString(e)));
-        try {
-          check_attn_error("attention");
-        } catch (const std::exception& x) {
-          r.set("error", Json::string(x.what()));
-        }
-        send_json(ctl_fd_, r);
+        reply_sync(hop_drain());
       } else {
         throw Error("unknown control message " + cmd);
       }
@@ -2374,102 +2389,41 @@ class Llama {
   // inboxes (uncached device memory, device-side hops) and prefill buffers exchanged as
   // IPC handles over the TCP control plane; ring: rank r sends to (r + 1) % world
   void connect_pipeline(const std::string& addr, double timeout_s) {
-    std::string host;
-    int port = 0;
-    split_host_port(addr, &host, &port);
     const int words = cake_hop_words(cfg_.H, 1, hop_bf16_ ? 1 : 0);
     // this rank's handles: its prefill buffer and one inbox per edge into it
     Json me = Json::object();
-    me.set("rank", Json::integer(rank_));
-    {
-      void* rp = nullptr;
-      k_check(cake_hop_alloc(sizeof(float) * (size_t)S_ * cfg_.H, &rp), "relay alloc");
-      relay_ = static_cast<float*>(rp);
-      hipIpcMemHandle_t hp;
-      hip_check(hipIpcGetMemHandle(&hp, relay_), "IpcGetMemHandle");
-      me.set("pbuf", Json::string(hex_of(&hp, sizeof(hp))));
-      Json ib = Json::array();
-      for (size_t e = 0; e < edges_.size(); ++e) {
-        if (edges_[e].second != rank_) continue;
-        void* p = nullptr;
-        k_check(cake_hop_alloc((size_t)words * 8, &p), "hop_alloc");
-        my_inbox_[(int)e] = p;
-        hipIpcMemHandle_t hi;
-        hip_check(hipIpcGetMemHandle(&hi, p), "IpcGetMemHandle");
-        Json x = Json::array();
-        x.push(Json::integer((int64_t)e));
-        x.push(Json::string(hex_of(&hi, sizeof(hi))));
-        ib.push(x);
-      }
-      me.set("inboxes", ib);
+    void* rp = nullptr;
+    k_check(cake_hop_alloc(sizeof(float) * (size_t)S_ * cfg_.H, &rp), "relay alloc");
+    relay_ = static_cast<float*>(rp);
+    me.set("pbuf", Json::string(ipc_export(relay_)));
+    Json ib = Json::array();
+    for (size_t e = 0; e < edges_.size(); ++e) {
+      if (edges_[e].second != rank_) continue;
+      void* p = nullptr;
+      k_check(cake_hop_alloc((size_t)words * 8, &p), "hop_alloc");
+      my_inbox_[(int)e] = p;
+      Json x = Json::array();
+      x.push(Json::integer((int64_t)e));
+      x.push(Json::string(ipc_export(p)));
+      ib.push(x);
     }
-    std::vector<Json> table(world_);
-    if (rank_ == 0) {
-      const int lfd = tcp_listen(host, port);
-      table[0] = me;
-      peers_.assign(world_ - 1, -1);
-      try {
-        for (int i = 1; i < world_; ++i) {
-          std::string peer;
-          const int fd = tcp_accept(lfd, &peer);
-          tcp_set_timeout(fd, 0);
-          const Json j = recv_json(fd);
-          const int r = (int)j.get("rank").as_int();
-          if (r < 1 || r >= world_ || peers_[r - 1] >= 0) throw Error("bad pipeline rank hello");
-          peers_[r - 1] = fd;
-          table[r] = j;
-        }
-      } catch (...) {
-        tcp_close(lfd);
-        throw;
-      }
-      tcp_close(lfd);
-      Json all = Json::array();
-      for (const auto& t : table) all.push(t);
-      Json m = Json::object();
-      m.set("table", all);
-      for (int fd : peers_) send_json(fd, m);
-    } else {
-      const auto deadline =
-          std::chrono::steady_clock::now() + std::chrono::duration<double>(timeout_s);
-      for (;;) {
-        try {
-          ctl_fd_ = tcp_connect(host, port, 2.0);
-          break;
-        } catch (const std::exception&) {
-          if (std::chrono::steady_clock::now() > deadline) throw;
-          usleep(200000);
-        }
-      }
-      tcp_set_timeout(ctl_fd_, 0);
-      send_json(ctl_fd_, me);
-      const Json m = recv_json(ctl_fd_);
-      for (int r = 0; r < world_; ++r) table[r] = m.get("table").at(r);
-    }
+    me.set("inboxes", ib);
+    ctl_.open(addr, rank_, world_, me, timeout_s, "bad pipeline rank hello");
     // map the receivers of this rank's outgoing edges: their inbox, their prefill buffer
     for (size_t e = 0; e < edges_.size(); ++e) {
       if (edges_[e].first != rank_) continue;
       const int dst = edges_[e].second;
-      const Json& t = table[dst];
+      const Json& t = ctl_.table()[dst];
       bool found = false;
       for (const auto& x : t.get("inboxes").items()) {
         if ((int)x.at(0).as_int() != (int)e) continue;
-        hipIpcMemHandle_t h;
-        unhex(x.at(1).as_string(), &h, sizeof(h));
-        void* p = nullptr;
-        hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "IpcOpen inbox");
-        out_inbox_[(int)e] = p;
+        out_inbox_[(int)e] = ipc_import(x.at(1).as_string(), "IpcOpen inbox");
         found = true;
       }
       if (!found) throw Error("rank " + std::to_string(dst) + " published no inbox for edge " +
                               std::to_string(e));
-      if (!peer_pbuf_.count(dst)) {
-        hipIpcMemHandle_t h;
-        unhex(t.get("pbuf").as_string(), &h, sizeof(h));
-        void* p = nullptr;
-        hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "IpcOpen pbuf");
-        peer_pbuf_[dst] = p;
-      }
+      if (!peer_pbuf_.count(dst))
+        peer_pbuf_[dst] = ipc_import(t.get("pbuf").as_string(), "IpcOpen pbuf");
     }
   }
 
@@ -2484,17 +2438,6 @@ class Llama {
   static bool selftest_forced_fail() {  // test hook: the fallback path of bench / cake-cli
     const char* e = std::getenv("CAKE_IPC_SELFTEST_FAIL");
     return e && *e == '1';
-  }
-
-  // every rank reaches this point, then every rank leaves it (rank 0 is the hub)
-  void ctl_barrier() {
-    if (rank_ == 0) {
-      for (int fd : peers_) (void)recv_json(fd);
-      for (int fd : peers_) send_json(fd, Json::object());
-    } else {
-      send_json(ctl_fd_, Json::object());
-      (void)recv_json(ctl_fd_);
-    }
   }
 
   // Each outgoing edge writes a pattern row into the receiver's relay buffer the way
@@ -2516,7 +2459,7 @@ class Llama {
                   "selftest relay");
         hip_check(hipStreamSynchronize(st_), "selftest sync");
       }
-      ctl_barrier();
+      ctl_.barrier();
       for (size_t e = 0; e < edges_.size(); ++e) {
         if (edges_[e].second != rank_ || (int)e >= S_) continue;
         hip_check(hipMemcpyAsync(hidden_ + H, relay_ + e * (size_t)H, sizeof(float) * H,
@@ -2532,7 +2475,7 @@ class Llama {
                 std::to_string(edges_[e].first) + " (edge " + std::to_string(e) + ", round " +
                 std::to_string(round) + ") delivered " + std::to_string(wrong) + " wrong words";
       }
-      ctl_barrier();
+      ctl_.barrier();
     }
   }
 
@@ -2586,23 +2529,8 @@ class Llama {
     selftest_relay(bad);
     if (bad.empty() && selftest_forced_fail())
       bad = "rank " + std::to_string(rank_) + ": failure forced by CAKE_IPC_SELFTEST_FAIL=1";
-    // verdicts to rank 0 (which fails the start naming every bad edge)
-    if (rank_ == 0) {
-      for (size_t i = 0; i < peers_.size(); ++i) {
-        const Json r = recv_json(peers_[i]);
-        if (r.has("bad") && bad.empty()) bad = r.get("bad").as_string();
-      }
-      Json v = Json::object();
-      v.set("ok", Json::boolean(bad.empty()));
-      if (!bad.empty()) v.set("bad", Json::string(bad));
-      for (int fd : peers_) send_json(fd, v);
-    } else {
-      Json r = Json::object();
-      if (!bad.empty()) r.set("bad", Json::string(bad));
-      send_json(ctl_fd_, r);
-      const Json v = recv_json(ctl_fd_);
-      if (v.has("bad")) bad = v.get("bad").as_string();
-    }
+    // verdicts to rank 0, which fails every rank's start with the first bad edge named
+    bad = ctl_.verdict(bad);
     if (!bad.empty()) throw Error("pipeline IPC self-test failed: " + bad);
   }
 
@@ -2661,50 +2589,13 @@ class Llama {
                                  hipMemcpyDeviceToDevice, st_), "slab copy");
       }
       hip_check(hipStreamSynchronize(st_), "sync");
-      tp_barrier();
+      ctl_.barrier();  // host barrier over the control sockets
       k_check(cake_sum_slices(hidden_ + off, slab_ + (size_t)bank * tp_ * SH, tp_, (long long)SH,
                               (long long)rows * cfg_.H, 1, st_), "sum_slices");
     }
   }
 
   int slab_rows() const { return std::min(S_, kSlabRows); }
-
-  // host barrier of the tensor-parallel ranks over the control sockets (star on rank 0)
-  void tp_barrier() {
-    if (tp_rank_ == 0) {
-      for (int fd : peers_) {
-        const Json j = recv_json(fd);
-        if (!j.has("cmd") || j.get("cmd").as_string() != "barrier") throw Error("TP barrier: bad message");
-      }
-      for (int fd : peers_) send_json(fd, msg("barrier"));
-    } else {
-      send_json(ctl_fd_, msg("barrier"));
-      const Json j = recv_json(ctl_fd_);
-      if (!j.has("cmd") || j.get("cmd").as_string() != "barrier") throw Error("TP barrier: bad message");
-    }
-  }
-
-  void sync_tp_workers() {
-    std::string err;
-    for (size_t i = 0; i < peers_.size(); ++i) {
-      try {
-        send_json(peers_[i], msg("sync"));
-        const Json r = recv_json(peers_[i]);
-        if (r.has("ar_err") && r.get("ar_err").as_int() != 0)
-          err = "tensor-parallel rank " + std::to_string(i + 1) + ": all-reduce timed out";
-        if (r.has("error")) err = r.get("error").as_string();
-      } catch (const std::exception& e) {
-        err = e.what();
-      }
-    }
-    int own[3] = {0, 0, 0};
-    hip_check(hipMemcpy(own, ar_err_, sizeof(own), hipMemcpyDeviceToHost), "ar_err");
-    if (own[0] | own[1] | own[2]) {
-      (void)hipMemset(ar_err_, 0, sizeof(own));
-      err = "tensor-parallel rank 0: all-reduce timed out";
-    }
-    if (!err.empty()) throw Error(err);
-  }
 
   static std::vector<int32_t> eos_of(const Json& m) {
     std::vector<int32_t> v;
@@ -2716,7 +2607,7 @@ class Llama {
   // worker rank: run the generations rank 0 announces, in lock step
   void serve_tp() {
     for (;;) {
-      const Json m = recv_json(ctl_fd_);
+      const Json m = ctl_.recv(0);
       const std::string cmd = m.get("cmd").as_string();
       if (cmd == "exit") break;
       if (cmd == "generate") {
@@ -2744,20 +2635,7 @@ class Llama {
         decode_tokens(L, (int)m.get("max_new").as_int(), eos.data(), (int)eos.size(), nullptr,
                       nullptr, nullptr, 0, false, nullptr);
       } else if (cmd == "sync") {
-        Json r = Json::object();
-        const hipError_t e = hipStreamSynchronize(st_);
-        int errs[3] = {0, 0, 0};
-        (void)hipMemcpy(errs, ar_err_, sizeof(errs), hipMemcpyDeviceToHost);
-        if (errs[0] | errs[1] | errs[2]) (void)hipMemset(ar_err_, 0, sizeof(errs));
-        r.set("ok", Json::boolean(e == hipSuccess));
-        r.set("ar_err", Json::integer(errs[0] | errs[1] | errs[2]));
-        if (e != hipSuccess) r.set("error", Json::string(hipGetErrorString(e)));
-        try {
-          check_attn_error("tensor-parallel rank " + std::to_string(tp_rank_));
-        } catch (const std::exception& x) {
-          r.set("error", Json::string(x.what()));
-        }
-        send_json(ctl_fd_, r);
+        reply_sync(ar_drain());
       } else {
         throw Error("unknown control message " + cmd);
       }
@@ -2854,30 +2732,13 @@ class Llama {
       hip_check(hipMemset(ar_err_, 0, sizeof(errs)), "memset");
     }
     if (selftest_forced_fail()) fail("failure forced by CAKE_IPC_SELFTEST_FAIL=1");
-    if (tp_rank_ == 0) {
-      for (int fd : peers_) {
-        const Json r = recv_json(fd);
-        if (r.has("bad") && bad.empty()) bad = r.get("bad").as_string();
-      }
-      Json v = Json::object();
-      if (!bad.empty()) v.set("bad", Json::string(bad));
-      for (int fd : peers_) send_json(fd, v);
-    } else {
-      Json r = Json::object();
-      if (!bad.empty()) r.set("bad", Json::string(bad));
-      send_json(ctl_fd_, r);
-      const Json v = recv_json(ctl_fd_);
-      if (v.has("bad")) bad = v.get("bad").as_string();
-    }
+    bad = ctl_.verdict(bad);
     if (!bad.empty()) throw Error("tensor-parallel IPC self-test failed: " + bad);
   }
 
   // channel inboxes (uncached, hop.hip granules) and the prefill slab, exchanged as IPC
   // handles through rank 0 (full mesh)
   void connect_tp(const std::string& addr, double timeout_s) {
-    std::string host;
-    int port = 0;
-    split_host_port(addr, &host, &port);
     auto alloc = [&](size_t words) {
       void* p = nullptr;
       k_check(cake_hop_alloc(words * 8, &p), "hop_alloc");
@@ -2896,57 +2757,8 @@ class Llama {
                       std::to_string(slab_bytes >> 20) + " MiB slab)");
     void* mine[4] = {ch_sum_.inbox, ch_key_.inbox, ch_gat_.inbox, slab_};
     Json me = Json::array();
-    for (void* p : mine) {
-      hipIpcMemHandle_t h;
-      hip_check(hipIpcGetMemHandle(&h, p), "IpcGetMemHandle");
-      me.push(Json::string(hex_of(&h, sizeof(h))));
-    }
-    std::vector<Json> table(tp_);
-    if (tp_rank_ == 0) {
-      table[0] = me;
-      const int lfd = tcp_listen(host, port);
-      peers_.assign(tp_ - 1, -1);
-      try {
-        for (int i = 1; i < tp_; ++i) {
-          std::string peer;
-          const int fd = tcp_accept(lfd, &peer);
-          tcp_set_timeout(fd, 0);
-          const Json j = recv_json(fd);
-          const int r = (int)j.get("rank").as_int();
-          if (r < 1 || r >= tp_ || peers_[r - 1] >= 0) throw Error("bad TP rank hello");
-          peers_[r - 1] = fd;
-          table[r] = j.get("h");
-        }
-      } catch (...) {
-        tcp_close(lfd);
-        throw;
-      }
-      tcp_close(lfd);
-      Json all = Json::array();
-      for (const auto& t : table) all.push(t);
-      Json m = Json::object();
-      m.set("table", all);
-      for (int fd : peers_) send_json(fd, m);
-    } else {
-      const auto deadline =
-          std::chrono::steady_clock::now() + std::chrono::duration<double>(timeout_s);
-      for (;;) {
-        try {
-          ctl_fd_ = tcp_connect(host, port, 2.0);
-          break;
-        } catch (const std::exception&) {
-          if (std::chrono::steady_clock::now() > deadline) throw;
-          usleep(200000);
-        }
-      }
-      tcp_set_timeout(ctl_fd_, 0);
-      Json hello = Json::object();
-      hello.set("rank", Json::integer(tp_rank_));
-      hello.set("h", me);
-      send_json(ctl_fd_, hello);
-      const Json m = recv_json(ctl_fd_);
-      for (int r = 0; r < tp_; ++r) table[r] = m.get("table").at(r);
-    }
+    for (void* p : mine) me.push(Json::string(ipc_export(p)));
+    ctl_.open(addr, tp_rank_, tp_, me, timeout_s, "bad TP rank hello");
     trace(rank(), "tensor-parallel handle table exchanged");
     ArChan* chans[3] = {&ch_sum_, &ch_key_, &ch_gat_};
     for (auto* ch : chans) ch->peers.assign(tp_, nullptr);
@@ -2954,10 +2766,7 @@ class Llama {
     for (int r = 0; r < tp_; ++r) {
       if (r == tp_rank_) continue;
       for (int k = 0; k < 4; ++k) {
-        hipIpcMemHandle_t h;
-        unhex(table[r].at(k).as_string(), &h, sizeof(h));
-        void* p = nullptr;
-        hip_check(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess), "IpcOpen");
+        void* p = ipc_import(ctl_.table()[r].at(k).as_string(), "IpcOpen");
         tp_mapped_.push_back(p);
         if (k < 3) chans[k]->peers[r] = p;
         else peer_slab_[r] = p;

@@ -463,16 +463,15 @@ class SdEngine {
   ~SdEngine() {
     for (auto& r : remote_)
       if (r.fd >= 0) tcp_close(r.fd);
-    for (int fd : speers_) {
+    for (int r = 1; r <= ctl_.workers(); ++r) {
       try {
         Json m = Json::object();
         m.set("cmd", Json::string("exit"));
-        send_json(fd, m);
+        ctl_.send(r, m);
       } catch (const std::exception&) {
       }
-      tcp_close(fd);
     }
-    if (ctl_fd_ >= 0) tcp_close(ctl_fd_);
+    ctl_.close();
     for (auto& c : chans_) {
       if (c.inbox) (void)cake_hop_free(c.inbox);
       if (c.peer) (void)hipIpcCloseMemHandle(c.peer);
@@ -1958,13 +1957,9 @@ class SdEngine {
   void connect_split(const CakeSdSplitOpts& sp) {
     split_plan(sp);
     stimeout_ = sp.timeout_s > 0 ? sp.timeout_s : 60.0;
-    std::string host;
-    int port = 0;
-    split_host_port(sp.master_addr ? sp.master_addr : "127.0.0.1:29533", &host, &port);
     serr_ = static_cast<int*>(dalloc(64));
     hip_check(hipMemset(serr_, 0, 64), "memset");
     Json me = Json::object();
-    me.set("rank", Json::integer(srank_));
     Json boxes = Json::array();
     for (size_t i = 0; i < chans_.size(); ++i) {
       Chan& c = chans_[i];
@@ -1974,66 +1969,21 @@ class SdEngine {
       c.cap = chan_bytes(c, rows_cap_);
       k_check(cake_hop_alloc(c.cap + 256, &c.inbox), "hop_alloc");
       hip_check(hipMemset(c.inbox, 0, c.cap + 256), "memset inbox");
-      hipIpcMemHandle_t h;
-      hip_check(hipIpcGetMemHandle(&h, c.inbox), "IpcGetMemHandle");
       Json e = Json::array();
       e.push(Json::integer((int64_t)i));
-      e.push(Json::string(hex_of(&h, sizeof(h))));
+      e.push(Json::string(ipc_export(c.inbox)));
       boxes.push(e);
     }
     me.set("inboxes", boxes);
-    std::vector<Json> table(sworld_);
-    if (srank_ == 0) {
-      const int lfd = tcp_listen(host, port);
-      table[0] = me;
-      speers_.assign(sworld_ - 1, -1);
-      try {
-        for (int i = 1; i < sworld_; ++i) {
-          std::string peer;
-          const int fd = tcp_accept(lfd, &peer);
-          tcp_set_timeout(fd, 0);
-          const Json j = recv_json(fd);
-          const int r = (int)j.get("rank").as_int();
-          if (r < 1 || r >= sworld_ || speers_[r - 1] >= 0) throw Error("split UNet: bad rank hello");
-          speers_[r - 1] = fd;
-          table[r] = j;
-        }
-      } catch (...) {
-        tcp_close(lfd);
-        throw;
-      }
-      tcp_close(lfd);
-      Json all = Json::array();
-      for (const auto& t : table) all.push(t);
-      Json m = Json::object();
-      m.set("table", all);
-      for (int fd : speers_) send_json(fd, m);
-    } else {
-      const double ct = sp.connect_timeout_s > 0 ? sp.connect_timeout_s : 600.0;
-      const auto deadline = std::chrono::steady_clock::now() + std::chrono::duration<double>(ct);
-      for (;;) {
-        try {
-          ctl_fd_ = tcp_connect(host, port, 2.0);
-          break;
-        } catch (const std::exception&) {
-          if (std::chrono::steady_clock::now() > deadline) throw;
-          std::this_thread::sleep_for(std::chrono::milliseconds(200));
-        }
-      }
-      tcp_set_timeout(ctl_fd_, 0);
-      send_json(ctl_fd_, me);
-      const Json m = recv_json(ctl_fd_);
-      for (int r = 0; r < sworld_; ++r) table[r] = m.get("table").at(r);
-    }
+    ctl_.open(sp.master_addr ? sp.master_addr : "127.0.0.1:29533", srank_, sworld_, me,
+              sp.connect_timeout_s > 0 ? sp.connect_timeout_s : 600.0, "split UNet: bad rank hello");
     for (size_t i = 0; i < chans_.size(); ++i) {
       Chan& c = chans_[i];
       if (c.src != srank_) continue;
       bool found = false;
-      for (const auto& x : table[c.dst].get("inboxes").items()) {
+      for (const auto& x : ctl_.table()[c.dst].get("inboxes").items()) {
         if ((size_t)x.at(0).as_int() != i) continue;
-        hipIpcMemHandle_t h;
-        unhex(x.at(1).as_string(), &h, sizeof(h));
-        hip_check(hipIpcOpenMemHandle(&c.peer, h, hipIpcMemLazyEnablePeerAccess), "IpcOpen inbox");
+        c.peer = ipc_import(x.at(1).as_string(), "IpcOpen inbox");
         found = true;
       }
       if (!found) throw Error("split UNet: rank " + std::to_string(c.dst) + " published no inbox");
@@ -2115,8 +2065,8 @@ class SdEngine {
     for (float t : ttab) tt.push(Json::number(t));
     m.set("ttab", tt);
     for (int r = 1; r < sused_; ++r) {
-      send_json(speers_[r - 1], m);
-      send_frame(speers_[r - 1], ctx.data(), (uint32_t)ctx.size());
+      ctl_.send(r, m);
+      send_frame(ctl_.fd(r), ctx.data(), (uint32_t)ctx.size());
     }
   }
 
@@ -2124,7 +2074,7 @@ class SdEngine {
   void split_finish() {
     std::string bad;
     for (int r = 1; r < sused_; ++r) {
-      const Json a = recv_json(speers_[r - 1]);
+      const Json a = ctl_.recv(r);
       if (bad.empty() && a.has("error")) bad = "split UNet rank " + std::to_string(r) + ": " +
                                                 a.get("error").as_string();
     }
@@ -2143,12 +2093,12 @@ class SdEngine {
     hip_check(hipSetDevice(dev_), "hipSetDevice");
     if (sworld_ < 2 || srank_ == 0) throw Error("serve() runs on split-UNet ranks > 0");
     for (;;) {
-      const Json m = recv_json(ctl_fd_);
+      const Json m = ctl_.recv(0);
       const std::string cmd = m.get("cmd").as_string();
       if (cmd == "exit") return;
       if (cmd != "gen") throw Error("split UNet: unknown control message " + cmd);
       const int n = (int)m.get("n").as_int(), B = (int)m.get("B").as_int();
-      const std::string ctx = recv_frame(ctl_fd_);
+      const std::string ctx = recv_frame(ctl_.fd(0));
       Json ack = Json::object();
       try {
         if (B < 1 || B > rows_cap_) throw Error("split UNet: " + std::to_string(B) +
@@ -2182,7 +2132,7 @@ class SdEngine {
         (void)hipStreamSynchronize(st_);
         ack.set("error", Json::string(x.what()));
       }
-      send_json(ctl_fd_, ack);
+      ctl_.send(0, ack);
     }
   }
 
@@ -2478,8 +2428,7 @@ class SdEngine {
   // split UNet (connect_split): this rank, its stages, the channels
   int srank_ = 0, sworld_ = 1, sused_ = 1, s_first_ = 0, s_end_ = 0;
   double stimeout_ = 60.0;
-  int ctl_fd_ = -1;
-  std::vector<int> speers_;
+  Star ctl_;  // control sockets of the split-UNet ranks, rank 0 the hub
   std::vector<int> sowner_, skip_prod_, skip_cons_;
   std::vector<Shp> x_shp_, skip_shp_;
   std::vector<Chan> chans_;

@@ -1,5 +1,6 @@
 // Native self-test of the C++ runtime (no GPU): JSON, topology, wire codec,
-// safetensors, framed TCP and the multi-threaded WorkerServer.
+// safetensors, framed TCP, the multi-threaded WorkerServer and the engines' control
+// star (star.h).
 //
 // Built three ways by scripts/sanitize_runtime.sh / tests/test_sanitizers_cpu.py:
 // plain, -fsanitize=address,undefined and -fsanitize=thread (host code only —
@@ -10,6 +11,7 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +25,7 @@
 #include "../runtime/proto.h"
 #include "../runtime/safetensors.h"
 #include "../runtime/server.h"
+#include "../runtime/star.h"
 #include "../runtime/topology.h"
 
 using namespace cake;
@@ -242,6 +245,191 @@ static void test_server() {
   CHECK(srv.stats().errors >= (uint64_t)kClients);
 }
 
+// ---- Star (star.h): the control plane of the multi-rank engines, one thread per rank.
+// The rank threads count into atomics; CHECK runs on the main thread after the joins.
+
+#if defined(__SANITIZE_ADDRESS__) || defined(__SANITIZE_THREAD__)
+constexpr double kSanitizerSlack = 2.0;
+#else
+constexpr double kSanitizerSlack = 1.0;
+#endif
+
+// a loopback address nobody listens on (the way WorkerServer gets its port: bind port 0)
+static std::string free_addr() {
+  const int fd = tcp_listen("127.0.0.1", 0);
+  const int port = tcp_local_port(fd);
+  tcp_close(fd);
+  return "127.0.0.1:" + std::to_string(port);
+}
+
+// distinct per rank; rank 2's is a bare string the size of an IPC handle (64 bytes) in hex
+static Json star_hello(int rank) {
+  if (rank == 2) {
+    std::string h;
+    for (int i = 0; i < 128; ++i) h += "0123456789abcdef"[(i * 7 + 3) % 16];
+    return Json::string(h);
+  }
+  Json j = Json::object();
+  j.set("who", Json::integer(100 + rank));
+  Json a = Json::array();
+  for (int i = 0; i <= rank; ++i) a.push(Json::string("box" + std::to_string(i * rank)));
+  j.set("inboxes", a);
+  return j;
+}
+
+// One thread per rank: the workers in `order` first, the hub hub_delay_ms after them (so
+// with a delay the workers take the connect retry path).  Each opens its Star, checks
+// the table and runs body(rank, star), which returns whether it saw what it should.
+// Returns the number of ranks that threw or saw something wrong.
+template <class F>
+static int star_world(const std::vector<int>& order, int hub_delay_ms, F body) {
+  const int world = (int)order.size() + 1;
+  const std::string addr = free_addr();
+  std::atomic<int> wrong{0};
+  auto run = [&](int rank) {
+    try {
+      Star s;
+      s.open(addr, rank, world, star_hello(rank), 20.0, "bad test rank hello");
+      bool good = (int)s.table().size() == world;
+      for (int r = 0; good && r < world; ++r) good = s.table()[r].dump() == star_hello(r).dump();
+      if (!good || !body(rank, s)) wrong++;
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "star rank %d threw: %s\n", rank, e.what());
+      wrong++;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int r : order) th.emplace_back(run, r);
+  std::this_thread::sleep_for(std::chrono::milliseconds(hub_delay_ms));
+  th.emplace_back(run, 0);
+  for (auto& t : th) t.join();
+  return wrong;
+}
+
+// The hub of `world` ranks against workers that claim the ranks in `claims`, the last of
+// them one it must refuse.  True if the hub threw the labelled message and, once it had
+// closed its sockets, every worker's read failed (so no thread stays blocked).
+static bool star_refuses(int world, const std::vector<int>& claims) {
+  const std::string addr = free_addr();
+  std::atomic<int> failed_reads{0};
+  std::vector<std::thread> th;
+  for (int claim : claims)
+    th.emplace_back([&, claim] {
+      try {
+        if (claim >= 1) {  // what a worker of that rank does
+          Star s;
+          s.open(addr, claim, world, star_hello(claim), 20.0, "bad test rank hello");
+        } else {  // Star takes rank 0 for the hub: say that hello by hand
+          int fd = -1;
+          for (int i = 0; fd < 0; ++i) {
+            try {
+              fd = tcp_connect("127.0.0.1", std::stoi(addr.substr(addr.rfind(':') + 1)), 2.0);
+            } catch (const std::exception&) {
+              if (i == 100) throw;
+              std::this_thread::sleep_for(std::chrono::milliseconds(50));
+            }
+          }
+          Json m = Json::object();
+          m.set("rank", Json::integer(claim));
+          m.set("hello", Json());
+          try {
+            send_json(fd, m);
+            (void)recv_json(fd);
+          } catch (...) {
+            tcp_close(fd);
+            throw;
+          }
+          tcp_close(fd);
+        }
+      } catch (const std::exception&) {
+        failed_reads++;
+      }
+    });
+  std::string said;
+  {
+    Star hub;
+    try {
+      hub.open(addr, 0, world, star_hello(0), 20.0, "bad test rank hello");
+    } catch (const std::exception& e) {
+      said = e.what();
+    }
+    hub.close();
+  }
+  for (auto& t : th) t.join();
+  return said == "bad test rank hello" && failed_reads == (int)claims.size();
+}
+
+static void test_star() {
+  // rendezvous at world 4: workers first and out of order, the hub 0.5 s later; then 100
+  // barrier rounds (nobody leaves round k before all 4 entered it) and the verdicts
+  std::atomic<int> entered{0};
+  const char* cases[4][4] = {{"", "", "", ""}, {"", "", "two", ""}, {"zero", "", "", "three"},
+                             {"", "one", "", "three"}};
+  const char* expect[4] = {"", "two", "zero", "one"};
+  CHECK(star_world({2, 3, 1}, 500, [&](int rank, Star& s) {
+          bool good = true;
+          for (int k = 1; k <= 100; ++k) {
+            entered++;
+            s.barrier();
+            good = good && entered.load() >= 4 * k;
+          }
+          for (int c = 0; c < 4; ++c) good = good && s.verdict(cases[c][rank]) == expect[c];
+          return good;
+        }) == 0);
+  CHECK(entered == 400);
+  // world 2, the smallest, the hub first
+  CHECK(star_world({1}, 0, [&](int rank, Star& s) {
+          s.barrier();
+          return s.verdict(rank == 1 ? "w" : "") == "w" && s.workers() == (rank == 0 ? 1 : 0);
+        }) == 0);
+
+  // refused hellos: a duplicate rank, a rank equal to world, rank 0
+  CHECK(star_refuses(3, {1, 1}));
+  CHECK(star_refuses(2, {2}));
+  CHECK(star_refuses(2, {0}));
+
+  // no hub: the worker gives up after the timeout, at most one attempt and one sleep late
+  {
+    const std::string addr = free_addr();
+    const auto t0 = std::chrono::steady_clock::now();
+    bool threw = false;
+    try {
+      Star s;
+      s.open(addr, 1, 2, star_hello(1), 0.5, "bad test rank hello");
+    } catch (const std::exception&) {
+      threw = true;
+    }
+    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    CHECK(threw);
+    CHECK(dt >= 0.5);
+    CHECK(dt <= (0.5 + 2.0 + 0.2) * kSanitizerSlack);
+  }
+
+  // a worker that sends something else where a barrier is due: the hub throws
+  std::atomic<int> hub_threw{0};
+  CHECK(star_world({1}, 0, [&](int rank, Star& s) {
+          if (rank == 1) {
+            Json m = Json::object();
+            m.set("cmd", Json::string("sync"));
+            s.send(0, m);
+            return true;
+          }
+          try {
+            s.barrier();
+          } catch (const std::exception&) {
+            hub_threw++;
+          }
+          return true;
+        }) == 0);
+  CHECK(hub_threw == 1);
+}
+
+// one line of output for both transport tests: tests/test_sanitizers_cpu.py counts them
+static void test_server_and_star() {
+  test_server();
+  test_star();
+}
+
 int main() {
   const struct {
     const char* name;
@@ -249,7 +437,7 @@ int main() {
   } tests[] = {{"topology", test_topology},
                {"proto", test_proto},
                {"safetensors", test_safetensors},
-               {"server", test_server}};
+               {"server+star", test_server_and_star}};
   for (const auto& t : tests) {
     try {
       t.fn();
