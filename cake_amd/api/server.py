@@ -18,6 +18,10 @@
   entries, bias in [-100, 100]) and ``min_p`` in [0, 1] (the native engine) act on the
   logits before token selection (``engine.LogitControls``); absent or neutral values change
   nothing, and a generator that cannot honour them answers 400 instead of ignoring them.
+  ``n`` in [1, 8] (the native engine on one GPU, 16-bit formats) returns ``n`` choices decoded
+  as one lock-step batch, choice ``i`` drawing with ``seed + i``, ``usage`` summed; 400 for an
+  out-of-range ``n`` and for ``n > 1`` with ``stream``, ``logprobs``, the logit controls or an
+  engine that does not batch; an absent ``n`` or ``n = 1`` is the single-sequence path.
 * ``POST /api/v1/image`` — body ``{"image_args": {...sd-* keys...}}``,
   returns ``{"images": [base64 PNG, ...]}`` (image.rs:15-68).
 * anything else → 404 with body ``nope`` (mod.rs:19-21,40).
@@ -85,6 +89,35 @@ def request_logprobs(body: dict) -> int | None:
         if not want:
             raise ValueError("top_logprobs needs logprobs: true")
     return (top or 0) if want else None
+
+
+N_MAX = 8   # completions of one request: the engine's lock-step batch (engine.MAX_BATCH)
+
+
+def request_n(body: dict) -> int:
+    """The request's ``n`` (completions): 1 when absent, else an integer in [1, 8].
+    ValueError on anything else."""
+    n = body.get("n")
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= N_MAX:
+        raise ValueError(f"n must be an integer in [1, {N_MAX}]")
+    return n
+
+
+def batch_refusal(body: dict, llm, want_lp, controls) -> str | None:
+    """Why a request with n > 1 cannot be served (never ignored), or None."""
+    if body.get("stream"):
+        return "n > 1 cannot be streamed"
+    if want_lp is not None:
+        return "n > 1 does not return logprobs"
+    if controls is not None:
+        return ("n > 1 does not apply presence_penalty, frequency_penalty, logit_bias or "
+                "min_p")
+    if not hasattr(llm, "generate_n"):
+        return ("n > 1 needs the native engine (a GPU, f16 / bf16, graphs on, "
+                "CAKE_NATIVE != 0)")
+    return llm.batch_refusal()
 
 
 def request_logit_controls(body: dict, vocab_size: int | None = None):
@@ -185,9 +218,38 @@ def create_app(master):
                                           "logit_bias and min_p need the native engine (a GPU, "
                                           "f16 / bf16, graphs on, CAKE_NATIVE != 0)"},
                                 status_code=400)
+        try:
+            n = request_n(body)
+        except ValueError as e:
+            return JSONResponse({"error": f"bad request: {e}"}, status_code=400)
         model_name = master.llm.MODEL_NAME
         rid, created = str(uuid.uuid4()), int(time.time())
         role = "Assistant" if _reference_roles() else "assistant"
+        if n > 1:  # n completions on one lock-step batch; n = 1 is the path below, untouched
+            why = batch_refusal(body, master.llm, want_lp, controls)
+            if why is not None:
+                return JSONResponse({"error": f"bad request: {why}"}, status_code=400)
+
+            def run_n():
+                with lock:
+                    master.reset()
+                    if sampling is not None:
+                        master.llm.set_sampling(sampling)
+                    for m in messages:
+                        master.llm.add_message(m)
+                    want = max_tokens if max_tokens is not None else master.ctx.args.sample_len
+                    return master.llm.generate_n(n, want)
+            import anyio
+            try:
+                outs = await anyio.to_thread.run_sync(run_n)
+            except RuntimeError as e:  # the engine's own refusal
+                return JSONResponse({"error": f"bad request: {e}"}, status_code=400)
+            return JSONResponse({
+                "id": rid, "object": "chat.completion", "created": created, "model": model_name,
+                "choices": [{"index": i, "message": {"role": role, "content": text},
+                             "finish_reason": "stop"} for i, (text, _) in enumerate(outs)],
+                "usage": {"completion_tokens": sum(c for _, c in outs)},
+            })
 
         def run(sink, on_token=None):
             with lock:

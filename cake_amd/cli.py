@@ -111,6 +111,12 @@ def build_parser() -> argparse.ArgumentParser:
            "[bos] + its tokens in consecutive windows of --max-seq-len, teacher forced; one "
            "JSON line {tokens, scored, windows, nll, ppl, top1} on stdout (any --weight-dtype "
            "/ --head-dtype / --kv-dtype / --prefill-dtype; not with --parallel tp)")
+    a("--prompts-file", default=None, metavar="PATH",
+      help="native Llama engine: decode the 1..8 lines of this UTF-8 text file as one "
+           "lock-step batch, each line treated as --prompt treats its text (sequence i draws "
+           "with --seed + i); one JSON line per prompt {index, n_prompt, tokens, text} on "
+           "stdout (16-bit weights, lm_head and KV cache on one GPU; not with --parallel tp, "
+           "a pipeline, topology workers, --logprobs-file or the logit-control flags)")
     a("--logprobs-file", default=None, metavar="PATH",
       help="native Llama engine: write one JSON line per generated token to PATH: {index, id, "
            "logprob, top_ids, top_logprobs}, over the logits token selection saw (after the "
@@ -238,6 +244,76 @@ def score_file_refusal(ctx) -> str | None:
     return None
 
 
+def prompts_file_refusal(ctx) -> str | None:
+    """Why this context cannot run ``--prompts-file`` (None: it can, or the option is off), in
+    the wording of :func:`score_file_refusal`: refused where the engine's generate_batch is."""
+    a = ctx.args
+    if not getattr(a, "prompts_file", None):
+        return None
+    native = ("--prompts-file is served by the native Llama engine only (a GPU, --dtype f16 or "
+              "bf16, hipGraph decode, CAKE_NATIVE not 0)")
+    if ctx.model_type != "text-model":
+        return native + ": it applies to the text model only"
+    if a.transport == "rccl":
+        return ("--prompts-file is not supported with --transport rccl: a pipeline or "
+                "tensor-parallel engine does not batch sequences")
+    if getattr(ctx, "score_file", None):
+        return "--prompts-file and --score-file exclude each other"
+    if getattr(a, "logprobs_file", None):
+        return "--prompts-file does not record logprobs: drop --logprobs-file"
+    try:
+        if cli_logit_controls(a) is not None:
+            return f"--prompts-file does not apply {LOGIT_CONTROL_FLAGS}"
+    except ValueError as e:
+        return str(e)
+    for flag, val in (("--weight-dtype", ctx.weight_dtype), ("--head-dtype", ctx.head_dtype),
+                      ("--kv-dtype", ctx.kv_dtype), ("--prefill-dtype", ctx.prefill_dtype)):
+        if val != "model":
+            return (f"--prompts-file runs 16-bit weights, lm_head and KV cache: not with "
+                    f"{flag} {val}")
+    if getattr(ctx.topology, "nodes", None):
+        return ("--prompts-file is not supported with topology workers: an engine with remote "
+                "workers does not batch sequences")
+    from .models.llama3.native_generator import native_eligible
+    if (not native_eligible(ctx) or a.transport != "tcp" or a.mode == "worker"
+            or getattr(a, "api", None)):
+        return native + ("; this run would take the Python path, which decodes one sequence at "
+                         "a time: refusing rather than generating")
+    return None
+
+
+def run_prompts_file(ctx) -> int:
+    """``--prompts-file``: one JSON line per prompt on stdout."""
+    import json
+
+    from .models.chat import Message
+    from .models.llama3.native_generator import NativeLLM
+    from .native_bridge import read_prompts_file
+    try:
+        lines = read_prompts_file(ctx.args.prompts_file)
+    except (OSError, ValueError) as e:
+        print(f"cake-cli: {e}", file=sys.stderr)
+        return 2
+    llm = NativeLLM.load(ctx)
+    try:
+        prompts = []
+        for line in lines:
+            llm.reset()
+            llm.add_message(Message.system(ctx.args.system_prompt))
+            llm.add_message(Message.user(line))
+            prompts.append(list(llm._prompt()))
+        room = llm.eng.max_seq - max(len(p) for p in prompts)
+        if room <= 0:
+            raise RuntimeError("prompt does not fit the KV cache (--max-seq-len)")
+        outs = llm.generate_prompts(prompts, min(int(ctx.args.sample_len), room))
+        for i, (p, toks) in enumerate(zip(prompts, outs)):
+            print(json.dumps({"index": i, "n_prompt": len(p), "tokens": toks,
+                              "text": llm.text_of(toks)}), flush=True)
+    finally:
+        llm.eng.close()
+    return 0
+
+
 def logprobs_file_refusal(ctx) -> str | None:
     """Why this context cannot run ``--logprobs-file`` / ``--top-logprobs`` (None: it can, or
     the options are off), in the wording of :func:`needs_native`."""
@@ -336,10 +412,13 @@ def _run(args) -> int:
     ctx = Context.from_args(args)
     why = (weight_dtype_refusal(ctx) or head_dtype_refusal(ctx) or kv_dtype_refusal(ctx)
            or prefill_dtype_refusal(ctx) or score_file_refusal(ctx)
+           or prompts_file_refusal(ctx)
            or logprobs_file_refusal(ctx) or logit_controls_refusal(ctx))
     if why:
         print(f"cake-cli: {why}", file=sys.stderr)
         return 2
+    if getattr(args, "prompts_file", None):
+        return run_prompts_file(ctx)
     if ctx.score_file:
         import json
 

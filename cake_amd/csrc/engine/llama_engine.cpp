@@ -443,6 +443,7 @@ class Llama {
     for (auto& kv : peer_pbuf_) (void)hipIpcCloseMemHandle(kv.second);
     for (auto& kv : my_inbox_) (void)cake_hop_free(kv.second);
     if (relay_) (void)cake_hop_free(relay_);
+    if (b_.host_tok) (void)hipHostFree(b_.host_tok);
     for (void* p : allocs_) (void)hipFree(p);
     (void)hipStreamDestroy(st_);
   }
@@ -691,6 +692,210 @@ class Llama {
       fill_stats(stats, L, n_out, 0.0, std::chrono::duration<double>(t1 - t0).count(), ms);
       // every token of a continuation is a decode step: the rate counts all of them
       stats->tokens_per_s = stats->decode_s > 0 ? n_out / stats->decode_s : 0.0;
+    }
+  }
+
+  // Lock-step batched decode of B <= 8 sequences: each prompt through the ordinary prefill
+  // into a KV set of its own (identical prompts once, the live rows copied), the first tokens
+  // from the prefill logits, then one step for all rows: embedding, per layer RMSNorm ->
+  // cake_gemv_rows (q|k|v, f32) -> cake_rope_kv_rows -> the batch-1 decode attention launch
+  // per sequence -> gemv_rows (o_proj into the f32 residual rows) -> RMSNorm -> gemv_rows
+  // (SwiGLU) -> gemv_rows (down_proj), the head as gemv_rows over [B, V], and the selection
+  // kernels once per sequence on that sequence's own state, sequence b drawing with seed + b.
+  // The weights are read once per step, not once per sequence.  Launched eagerly; the host
+  // reads the tokens one step behind.  Every row's arithmetic is independent of B and of the
+  // row's slot, so a sequence's tokens are those of the same prompt decoded alone.  A sequence
+  // that met EOS keeps its row until the others end; nothing more of it is reported.
+  // logits_out (tests): [B, max_new, V], the rows token selection saw; rows at and past
+  // out_len[b] are unspecified.
+  void generate_batch(const int32_t* tokens, const int32_t* offsets, int B, int max_new,
+                      const CakeEngineSampling& smp, const int32_t* eos, int n_eos, int32_t* out,
+                      int32_t* out_len, CakeEngineStats* seq_stats, CakeEngineStats* stats,
+                      float* logits_out) {
+    hip_check(hipSetDevice(dev_), "hipSetDevice");
+    const char* who = "generate_batch() runs on a single-rank engine with 16-bit weights: not ";
+    if (world_ > 1) throw Error(std::string(who) + "on a pipeline engine");
+    if (tp_ > 1) throw Error(std::string(who) + "on a tensor-parallel engine");
+    if (remote_mode()) throw Error(std::string(who) + "on an engine with remote workers");
+    if (!head_ || (int)owned_.size() != cfg_.L)
+      throw Error(std::string(who) + "on a layers-only engine");
+    if (wfmt_ != kFmt16)
+      throw Error(std::string(who) + "with " + fmt_facts(wfmt_).name + " weights (weight_fmt " +
+                  std::to_string(wfmt_) + ")");
+    if (hfmt_ != kFmt16)
+      throw Error(std::string(who) + "with an " + fmt_facts(hfmt_).name + " lm_head (head_fmt " +
+                  std::to_string(hfmt_) + ")");
+    if (kvfmt_ != kKv16)
+      throw Error(std::string(who) + "with a quantised KV cache (kv_fmt " + std::to_string(kvfmt_) +
+                  ")");
+    if (lp_k_ >= 0) throw Error("generate_batch() does not record logprobs: turn them off first");
+    if (lc_next_.on)
+      throw Error("generate_batch() does not apply logit controls: turn them off first");
+    if (B < 1 || B > kMaxBatch)
+      throw Error("generate_batch() takes 1 to " + std::to_string(kMaxBatch) + " prompts, got " +
+                  std::to_string(B));
+    const Cfg& c = cfg_;
+    const int nq = c.nh * c.hd;
+    if (c.H % 32 || nq % 32 || c.I % 32 || c.V % 4)
+      throw Error("generate_batch() needs hidden, attention and intermediate widths divisible by "
+                  "32 and a vocabulary divisible by 4");
+    std::vector<int> T(B);
+    for (int b = 0; b < B; ++b) {
+      T[b] = offsets[b + 1] - offsets[b];
+      if (T[b] <= 0) throw Error("generate_batch(): empty prompt (sequence " + std::to_string(b) + ")");
+      if (max_new > 0 && (int64_t)T[b] + max_new > S_)
+        throw Error("generate_batch(): prompt + max_new exceeds max_seq (sequence " +
+                    std::to_string(b) + ": " + std::to_string(T[b]) + " + " +
+                    std::to_string(max_new) + " > " + std::to_string(S_) + ")");
+      for (int i = offsets[b]; i < offsets[b + 1]; ++i)
+        if (tokens[i] < 0 || tokens[i] >= c.V)
+          throw Error("generate_batch(): token id " + std::to_string(tokens[i]) +
+                      " is outside [0, " + std::to_string(c.V) + ")");
+    }
+    for (int b = 0; b < B; ++b) out_len[b] = 0;
+    if (max_new <= 0) return;
+    batch_alloc(B);
+    Mode mode = mode_of(smp);
+    mode.fused = false;
+    struct Restore {  // the generation's own cache and launch choice, whatever happens
+      Llama* s;
+      ~Restore() {
+        s->cur_ = s->kv_.at(0);
+        s->short_step_ = false;
+      }
+    } restore{this};
+    const size_t V = c.V;
+    const auto t0 = std::chrono::steady_clock::now();
+    // ---- prefill: distinct prompts once each; src[b] = the first sequence with b's prompt
+    std::vector<int> src(B);
+    for (int b = 0; b < B; ++b) {
+      src[b] = b;
+      for (int a = 0; a < b && src[b] == b; ++a)
+        if (src[a] == a && T[a] == T[b] &&
+            std::equal(tokens + offsets[a], tokens + offsets[a + 1], tokens + offsets[b]))
+          src[b] = a;
+    }
+    std::vector<int32_t> h_len(B), h_pos(B);
+    for (int b = 0; b < B; ++b) {
+      h_len[b] = T[b];
+      h_pos[b] = T[b] - 1;
+      hip_check(hipMemcpyAsync(b_.hist + (size_t)b * S_, tokens + offsets[b], sizeof(int32_t) * T[b],
+                               hipMemcpyHostToDevice, st_), "hist H2D");
+    }
+    hip_check(hipMemcpyAsync(b_.hist_len, h_len.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice,
+                             st_), "hist_len H2D");
+    hip_check(hipMemcpyAsync(b_.pos, h_pos.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, st_),
+              "pos H2D");
+    hip_check(hipMemsetAsync(b_.slot, 0, sizeof(unsigned long long) * kMaxBatch, st_), "slot");
+    hip_check(hipStreamSynchronize(st_), "sync");  // h_len / h_pos are read by the copies
+    const size_t row_bytes = (size_t)lc_.hd * kv_esize();
+    for (int b = 0; b < B; ++b) {
+      if (src[b] != b) continue;
+      cur_ = b_.kv[b];
+      prefill_body(tokens + offsets[b], T[b]);
+      head_gemv(hidden_ + (size_t)(T[b] - 1) * c.H);
+      for (int d = b; d < B; ++d) {
+        if (src[d] != b) continue;
+        hip_check(hipMemcpyAsync(b_.logits + (size_t)d * V, logits_, sizeof(float) * V,
+                                 hipMemcpyDeviceToDevice, st_), "logits D2D");
+        if (d == b) continue;
+        // rows [0, T) of every (layer, kv head) of the prefilled caches
+        const size_t pitch = (size_t)S_ * row_bytes, width = (size_t)T[b] * row_bytes;
+        const size_t height = owned_.size() * (size_t)lc_.nkv;
+        hip_check(hipMemcpy2DAsync(b_.kv[d].k, pitch, b_.kv[b].k, pitch, width, height,
+                                   hipMemcpyDeviceToDevice, st_), "k prefix D2D");
+        hip_check(hipMemcpy2DAsync(b_.kv[d].v, pitch, b_.kv[b].v, pitch, width, height,
+                                   hipMemcpyDeviceToDevice, st_), "v prefix D2D");
+      }
+    }
+    // ---- first tokens, from the prefill logits
+    auto mode_of_seq = [&](int b) {
+      Mode m = mode;
+      if (!m.greedy) m.seed = smp.seed + (uint64_t)b;
+      return m;
+    };
+    auto select_all = [&]() {
+      for (int b = 0; b < B; ++b)
+        select_tail(mode_of_seq(b), {b_.logits + (size_t)b * V, b_.hist + (size_t)b * S_,
+                                     b_.hist_len + b, b_.tok + b, b_.pos + b, b_.slot + b});
+    };
+    auto keep_logits = [&](int i) {  // token index i of every sequence
+      if (!logits_out) return;
+      for (int b = 0; b < B; ++b)
+        hip_check(hipMemcpyAsync(logits_out + ((size_t)b * max_new + i) * V,
+                                 b_.logits + (size_t)b * V, sizeof(float) * V,
+                                 hipMemcpyDeviceToHost, st_), "logits D2H");
+    };
+    select_all();
+    keep_logits(0);
+    hip_check(hipMemcpyAsync(b_.host_tok, b_.tok, sizeof(int32_t) * B, hipMemcpyDeviceToHost, st_),
+              "tok D2H");
+    hip_check(hipStreamSynchronize(st_), "sync");
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<char> done(B, 0);
+    int live = B;
+    auto take = [&](int i, const int32_t* toks) {  // token index i as read back
+      for (int b = 0; b < B; ++b) {
+        if (done[b]) continue;
+        out[(size_t)b * max_new + i] = toks[b];
+        out_len[b] = i + 1;
+        for (int e = 0; e < n_eos; ++e)
+          if (eos[e] == toks[b]) done[b] = 1;
+        if (done[b]) --live;
+      }
+    };
+    take(0, b_.host_tok);
+    // ---- steps: token index i comes from step i; the host reads step i - 1 while step i runs
+    std::vector<hipEvent_t> ev;
+    struct Events {
+      std::vector<hipEvent_t>& v;
+      ~Events() { for (hipEvent_t e : v) (void)hipEventDestroy(e); }
+    } events{ev};
+    auto mark = [&]() {
+      hipEvent_t e;
+      hip_check(hipEventCreate(&e), "hipEventCreate");
+      ev.push_back(e);
+      hip_check(hipEventRecord(e, st_), "hipEventRecord");
+    };
+    mark();
+    int launched = 0, taken = 0;  // steps
+    auto take_step = [&](int i) {
+      hip_check(hipEventSynchronize(ev[i]), "hipEventSynchronize");
+      take(i, b_.host_tok + (i & 1) * kMaxBatch);
+      taken = i;
+    };
+    for (int i = 1; i < max_new && live > 0; ++i) {
+      batch_step(B, T, i);
+      select_all();
+      keep_logits(i);
+      hip_check(hipMemcpyAsync(b_.host_tok + (i & 1) * kMaxBatch, b_.tok, sizeof(int32_t) * B,
+                               hipMemcpyDeviceToHost, st_), "tok D2H");
+      mark();
+      launched = i;
+      if (i >= 2) take_step(i - 1);
+    }
+    if (launched > taken && live > 0) take_step(launched);
+    hip_check(hipStreamSynchronize(st_), "sync");
+    const auto t2 = std::chrono::steady_clock::now();
+    check_attn_error("generate_batch");
+    std::vector<float> ms;
+    for (int i = 1; i <= launched; ++i) {
+      float t = 0.f;
+      hip_check(hipEventElapsedTime(&t, ev[i - 1], ev[i]), "hipEventElapsedTime");
+      ms.push_back(t);
+    }
+    const double prefill_s = std::chrono::duration<double>(t1 - t0).count();
+    const double decode_s = std::chrono::duration<double>(t2 - t1).count();
+    int n_prompt = 0, n_gen = 0, n_steps = 0;
+    for (int b = 0; b < B; ++b) {
+      if (seq_stats) fill_stats(seq_stats + b, T[b], out_len[b], prefill_s, decode_s, ms);
+      n_prompt += T[b];
+      n_gen += out_len[b];
+      n_steps += out_len[b] - 1;
+    }
+    if (stats) {
+      fill_stats(stats, n_prompt, n_gen, prefill_s, decode_s, ms);
+      stats->tokens_per_s = decode_s > 0 ? n_steps / decode_s : 0.0;  // all sequences together
     }
   }
 
@@ -1088,6 +1293,18 @@ class Llama {
   std::vector<int32_t> bucket_of_;
   Mode graph_mode_, last_mode_;
   bool have_graphs_ = false;
+  // lock-step batched decode (generate_batch): nothing of it exists before the first call
+  static constexpr int kMaxBatch = 8;
+  struct BatchState {
+    std::vector<KV> kv;  // one K / V cache set per sequence
+    float *resid = nullptr, *qkv32 = nullptr, *q = nullptr, *logits = nullptr;  // [8, ...] rows
+    float* logits2 = nullptr;  // [16, V]: the head's two partial rows per sequence
+    uint16_t *x16 = nullptr, *attn = nullptr, *act = nullptr;  // x16: [16, H]
+    int *tok = nullptr, *pos = nullptr, *hist = nullptr, *hist_len = nullptr;  // hist: [8, S]
+    unsigned long long* slot = nullptr;
+    void **kbase = nullptr, **vbase = nullptr;  // device tables of the sequences' cache bases
+    int32_t* host_tok = nullptr;                // pinned: two rows of 8, the read-back ring
+  } b_;
 
   template <class T> T* dalloc(size_t n) {
     void* p = nullptr;
@@ -1839,29 +2056,37 @@ class Llama {
     set_i32(reinterpret_cast<int*>(lc_state_ + 1), n_prompt);
   }
 
+  // the device state one sequence's token selection reads and moves
+  struct SelState {
+    float* logits;
+    int *hist, *hist_len, *tok, *pos;
+    unsigned long long* slot;
+  };
+
   // logits -> penalty -> logit controls -> argmax / draw -> finalize (tok, history, pos)
-  void select_tail(const Mode& m) {
+  void select_tail(const Mode& m) { select_tail(m, {logits_, hist_, hist_len_, tok_, pos_, slot_}); }
+  void select_tail(const Mode& m, const SelState& s) {
     if (m.penalty != 1.f)
-      k_check(cake_repeat_penalty(logits_, hist_, hist_len_, m.last_n, m.penalty, st_), "penalty");
+      k_check(cake_repeat_penalty(s.logits, s.hist, s.hist_len, m.last_n, m.penalty, st_), "penalty");
     if (m.controls)  // counts hist_[counted, hist_len) first: before finalize moves hist_len
-      k_check(cake_logit_controls(logits_, lc_.V, hist_, hist_len_, lc_cnt_, lc_params_, lc_state_,
+      k_check(cake_logit_controls(s.logits, lc_.V, s.hist, s.hist_len, lc_cnt_, lc_params_, lc_state_,
                                   0, st_), "logit_controls");
     if (m.greedy) {
-      k_check(cake_argmax(logits_, lc_.V, slot_, st_), "argmax");
+      k_check(cake_argmax(s.logits, lc_.V, s.slot, st_), "argmax");
     } else {
       const bool restrict = m.top_k > 0 || m.top_p > 0.f;
       if (restrict)
-        k_check(cake_sample_threshold(logits_, lc_.V, m.temperature, m.top_k, m.top_p, thr_, st_),
+        k_check(cake_sample_threshold(s.logits, lc_.V, m.temperature, m.top_k, m.top_p, thr_, st_),
                 "sample_threshold");
       const unsigned int* thr = restrict ? thr_ : nullptr;
       if (m.min_p) {  // the sets intersect: the larger key
         if (restrict) k_check(cake_logit_controls_merge_thr(thr_, lc_state_ + 2, st_), "merge_thr");
         else thr = lc_state_ + 2;
       }
-      k_check(cake_gumbel_argmax(logits_, lc_.V, m.temperature, m.seed, hist_len_, thr, slot_, st_),
-              "gumbel_argmax");
+      k_check(cake_gumbel_argmax(s.logits, lc_.V, m.temperature, m.seed, s.hist_len, thr, s.slot,
+                                 st_), "gumbel_argmax");
     }
-    k_check(cake_finalize_token(slot_, tok_, hist_, hist_len_, pos_, S_, st_), "finalize");
+    k_check(cake_finalize_token(s.slot, s.tok, s.hist, s.hist_len, s.pos, S_, st_), "finalize");
   }
 
   // the record of the token just finalised: logits_ still holds the row selection saw (the
@@ -1954,17 +2179,18 @@ class Llama {
 
   // decode attention of local layer l into attn_out_: over the fp8 code cache (kv_fmt 1),
   // head-parallel for a short context, split over the context otherwise
-  void attn(int l) {
+  void attn(int l) { attn(l, q_, pos_, attn_out_); }
+  void attn(int l, const float* q, const int* pos, void* out) {
     const Cfg& c = lc_;
     if (kvfmt_ == kKvFp8)
-      k_check(cake_attn_decode_kv8(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                                   part_, tickets_, attn_out_, st_), "attn_decode_kv8");
+      k_check(cake_attn_decode_kv8(dt_, q, kc(l), vc(l), pos, S_, c.nh, c.nkv, c.hd, scale(),
+                                   part_, tickets_, out, st_), "attn_decode_kv8");
     else if (short_step_)
-      k_check(cake_attn_decode_heads(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd,
-                                     scale(), attn_out_, st_), "attn_heads");
+      k_check(cake_attn_decode_heads(dt_, q, kc(l), vc(l), pos, S_, c.nh, c.nkv, c.hd,
+                                     scale(), out, st_), "attn_heads");
     else
-      k_check(cake_attn_decode(dt_, q_, kc(l), vc(l), pos_, S_, c.nh, c.nkv, c.hd, scale(),
-                               part_, tickets_, attn_out_, st_), "attn_decode");
+      k_check(cake_attn_decode(dt_, q, kc(l), vc(l), pos, S_, c.nh, c.nkv, c.hd, scale(),
+                               part_, tickets_, out, st_), "attn_decode");
   }
 
   // every GEMV through its dispatcher (llama_weights.h: the entry point of the matrix's format
@@ -1993,6 +2219,85 @@ class Llama {
       k_check(gemv_x16(dt_, act_, w.d, c.I, c.H, out, accumulate, st_), "down_proj", w.d);
       if (tp_ > 1) ar_sum();
     }
+  }
+
+  // ---- lock-step batched decode
+  void batch_alloc(int B) {
+    const Cfg& c = lc_;
+    const size_t nq = (size_t)c.nh * c.hd, nk = (size_t)c.nkv * c.hd, R = kMaxBatch;
+    if (!b_.resid) {
+      b_.resid = dalloc<float>(R * c.H);
+      b_.qkv32 = dalloc<float>(R * (nq + 2 * nk));
+      b_.q = dalloc<float>(R * nq);
+      b_.logits = dalloc<float>(R * c.V);
+      b_.logits2 = dalloc<float>(2 * R * c.V);
+      b_.x16 = dalloc<uint16_t>(2 * R * c.H);
+      b_.attn = dalloc<uint16_t>(R * nq);
+      b_.act = dalloc<uint16_t>(R * c.I);
+      b_.tok = dalloc<int>(R);
+      b_.pos = dalloc<int>(R);
+      b_.hist = dalloc<int>(R * S_);
+      b_.hist_len = dalloc<int>(R);
+      b_.slot = dalloc<unsigned long long>(R);
+      b_.kbase = dalloc<void*>(R);
+      b_.vbase = dalloc<void*>(R);
+      hip_check(hipHostMalloc(reinterpret_cast<void**>(&b_.host_tok), sizeof(int32_t) * 2 * R,
+                              hipHostMallocDefault), "hipHostMalloc");
+    }
+    while ((int)b_.kv.size() < B) {
+      const size_t n = kv_elems() * kv_esize();
+      b_.kv.push_back(KV{dalloc<uint8_t>(n), dalloc<uint8_t>(n)});
+    }
+    std::vector<void*> kb(R, nullptr), vb(R, nullptr);
+    for (size_t b = 0; b < b_.kv.size(); ++b) {
+      kb[b] = b_.kv[b].k;
+      vb[b] = b_.kv[b].v;
+    }
+    hip_check(hipMemcpyAsync(b_.kbase, kb.data(), sizeof(void*) * R, hipMemcpyHostToDevice, st_),
+              "kbase H2D");
+    hip_check(hipMemcpyAsync(b_.vbase, vb.data(), sizeof(void*) * R, hipMemcpyHostToDevice, st_),
+              "vbase H2D");
+    hip_check(hipStreamSynchronize(st_), "sync");
+  }
+
+  // one step of B rows: token index i of every sequence (device position T[b] + i - 1), up to
+  // the [B, V] logits; the caller selects
+  void batch_step(int B, const std::vector<int>& T, int i) {
+    const Cfg& c = lc_;
+    const int nq = c.nh * c.hd, nqkv = nq + 2 * c.nkv * c.hd;
+    const float eps = (float)c.eps;
+    auto rows = [&](int epi, const void* x, int K, const Mat& m, void* o, long long ldo,
+                    float* resid, int N, const char* what) {
+      k_check(cake_gemv_rows(dt_, epi, x, K, m.w, K, o, ldo, resid, resid ? N : 0, B, N, K, st_),
+              what);
+    };
+    k_check(cake_embed(dt_, embed_, b_.tok, B, c.H, b_.resid, st_), "embed");
+    for (size_t l = 0; l < layers_.size(); ++l) {
+      const LayerW& w = layers_[l];
+      k_check(cake_rmsnorm(dt_, b_.resid, w.ln1, eps, B, c.H, b_.x16, st_), "rmsnorm");
+      rows(kEpiStore32, b_.x16, c.H, w.qkv, b_.qkv32, nqkv, nullptr, nqkv, "gemv_rows qkv");
+      k_check(cake_rope_kv_rows(dt_, b_.qkv32, nqkv, B, b_.pos, inv_freq_, c.nh, c.nkv, c.hd, S_,
+                                b_.q, b_.kbase, b_.vbase, (long long)l * c.nkv * S_ * c.hd, st_),
+              "rope_kv_rows");
+      for (int b = 0; b < B; ++b) {  // the launch a batch-1 step picks at this sequence's length
+        cur_ = b_.kv[b];
+        short_step_ = heads_max_ > 0 && short_at(T[b] + i - 1);
+        attn((int)l, b_.q + (size_t)b * nq, b_.pos + b, b_.attn + (size_t)b * nq);
+      }
+      short_step_ = false;
+      rows(kEpiResid32, b_.attn, nq, w.o, nullptr, 0, b_.resid, c.H, "gemv_rows o_proj");
+      k_check(cake_rmsnorm(dt_, b_.resid, w.ln2, eps, B, c.H, b_.x16, st_), "rmsnorm");
+      rows(kEpiSwiglu, b_.x16, c.H, w.gu, b_.act, c.I, nullptr, c.I, "gemv_rows gate|up");
+      rows(kEpiResid32, b_.act, c.I, w.d, nullptr, 0, b_.resid, c.H, "gemv_rows down_proj");
+    }
+    // the head on the f32 normalised rows as two 16-bit terms each (the batch-1 head reads
+    // them in f32): 2B rows on one pass over the head, then the two f32 sums added
+    k_check(cake_rmsnorm_split_rows(dt_, b_.resid, norm_, eps, B, c.H, b_.x16, st_),
+            "rmsnorm_split_rows");
+    k_check(cake_gemv_rows(dt_, kEpiStore32, b_.x16, c.H, lm_head_.w, c.H, b_.logits2, c.V, nullptr,
+                           0, 2 * B, c.V, c.H, st_), "gemv_rows lm_head");
+    k_check(cake_sum_slices(b_.logits, b_.logits2, 2, (long long)B * c.V, (long long)B * c.V, 0,
+                            st_), "sum_slices");
   }
 
   void step_head(const Mode& m) {
@@ -3021,6 +3326,25 @@ CAKE_API int32_t cake_engine_generate(void* h, const int32_t* prompt, int32_t n_
     if (!h || !prompt || !sampling || (!out && max_new > 0)) throw cake::Error("null argument");
     static_cast<Llama*>(h)->generate(prompt, n_prompt, max_new, *sampling, eos, n_eos, cb, ctx,
                                      out, out_cap, stats);
+    return 0;
+  } catch (const std::exception& e) {
+    cake::put_err(err, errlen, e.what());
+    return 1;
+  }
+}
+
+CAKE_API int32_t cake_engine_generate_batch(void* h, const int32_t* tokens, const int32_t* offsets,
+                                            int32_t n_seq, int32_t max_new,
+                                            const CakeEngineSampling* sampling, const int32_t* eos,
+                                            int32_t n_eos, int32_t* out, int32_t* out_len,
+                                            CakeEngineStats* seq_stats, CakeEngineStats* stats,
+                                            float* logits_out, char* err, int32_t errlen) {
+  try {
+    if (!h || !tokens || !offsets || !sampling || !out_len || (!out && max_new > 0) ||
+        (!eos && n_eos > 0))
+      throw cake::Error("null argument");
+    static_cast<Llama*>(h)->generate_batch(tokens, offsets, n_seq, max_new, *sampling, eos, n_eos,
+                                           out, out_len, seq_stats, stats, logits_out);
     return 0;
   } catch (const std::exception& e) {
     cake::put_err(err, errlen, e.what());

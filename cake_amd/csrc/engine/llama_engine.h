@@ -189,6 +189,28 @@ int32_t cake_engine_generate(void* engine, const int32_t* prompt, int32_t n_prom
                              const int32_t* eos, int32_t n_eos, cake_engine_token_cb cb,
                              void* ctx, int32_t* out, int32_t out_cap,
                              struct CakeEngineStats* stats, char* err, int32_t errlen);
+// Lock-step batched decode of n_seq prompts, 1 <= n_seq <= 8: prompt b is
+// tokens[offsets[b], offsets[b + 1]) (offsets: n_seq + 1 entries).  Each prompt is prefilled
+// into a KV cache of its own (identical prompts once), the first tokens come from the prefill
+// logits, then every step decodes all sequences on one pass over the weights.  One sampling
+// setting; sequence b draws with seed + b.  A sequence's tokens are bit for bit those of the
+// same prompt decoded alone through this call (with seed + b), whatever else rides in the
+// batch.  out[b * max_new + i]: token i of sequence b, out_len[b] of them (its EOS inclusive;
+// a sequence that ended keeps its row until all have ended or max_new is reached).
+// seq_stats [n_seq] or null (per sequence: n_prompt, n_generated, its rate; the times are the
+// call's); stats or null (sums, tokens_per_s of all sequences together, p50 / p99 device ms
+// per step).  logits_out: null, or f32 [n_seq, max_new, V] for the rows token selection saw
+// (tests; rows at and past out_len[b] are unspecified).  cake_engine_open with weight_fmt 0,
+// head_fmt 0 and kv_fmt 0 only; refused (message in err) before any launch: pipeline,
+// tensor-parallel, remote and layers-only engines, quantised weights / head / KV cache,
+// logprobs or logit controls turned on, n_seq outside 1..8, an empty prompt,
+// n_prompt + max_new > max_seq.  Leaves cake_engine_generate / continue state untouched.
+int32_t cake_engine_generate_batch(void* engine, const int32_t* tokens, const int32_t* offsets,
+                                   int32_t n_seq, int32_t max_new,
+                                   const struct CakeEngineSampling* sampling, const int32_t* eos,
+                                   int32_t n_eos, int32_t* out, int32_t* out_len,
+                                   struct CakeEngineStats* seq_stats, struct CakeEngineStats* stats,
+                                   float* logits_out, char* err, int32_t errlen);
 // Continue the last generation for up to max_new more tokens (same sampling, the device
 // state where the previous generate / continue left it, EOS included): chat turns that
 // extend a context, and benchmarks that time exactly max_new decode steps.

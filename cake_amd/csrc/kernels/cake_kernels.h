@@ -220,6 +220,28 @@ int cake_swiglu_p13(int dt, const float* resid, const void* norm_w, float eps, c
 int cake_gemv_x16_p13(int dt, const void* x, const void* planes, const int* hdr, const void* raw,
                       int K, int N, float* out, int accumulate, hipStream_t st);
 
+// ---- kernels/gemv_rows.hip: the projections of a lock-step batched decode step ---------
+// epi: kEpiStore32, kEpiResid32 or kEpiSwiglu; tiles 1 / 2 / 4 (swiglu 1 / 2), unroll 2 / 4
+int cake_gemv_rows_set_tuning(int epi, int tiles, int unroll, int max_blocks);
+int cake_gemv_rows_get_tuning(int epi, int* out3);
+// x16 [M, K] (dt) times the 16-bit rows w [N, K], 1 <= M <= 16, K % 32 == 0, ldx and ldw
+// multiples of 8.  store32: out f32 [M, N] = sum; resid32: resid32 f32 [M, N] += sum;
+// swiglu: out 16-bit [M, N] = silu(w[n] . x) * (w[N + n] . x), w the packed [2N, K].
+int cake_gemv_rows(int dt, int epi, const void* x16, long long ldx, const void* w, long long ldw,
+                   void* out, long long ldo, float* resid32, long long ldr, int M, int N, int K,
+                   hipStream_t st);
+// RMSNorm of x f32 [M, H], M <= 8, as two 16-bit terms, out16 [2M, H]: row m = cake_rmsnorm's
+// row, row M + m = the rounded remainder of the f32 value (the batched lm_head's operand)
+int cake_rmsnorm_split_rows(int dt, const float* x, const void* w, float eps, int M, int H,
+                            void* out16, hipStream_t st);
+// qkv32 f32 [M, (nh + 2 nkv) hd] -> q_out f32 [M, nh hd] roped, k roped and v into row pos[m]
+// of the 16-bit caches at kbase[m] / vbase[m] + layer_off elements ([nkv][S][hd]); pos, kbase
+// and vbase are device arrays of M entries; a row with pos[m] outside [0, S) writes nothing
+int cake_rope_kv_rows(int dt, const float* qkv32, long long ldq, int M, const int* pos,
+                      const float* inv_freq, int nh, int nkv, int hd, int S, float* q_out,
+                      void* const* kbase, void* const* vbase, long long layer_off,
+                      hipStream_t st);
+
 // ---- kernels/gemv_w4.hip: MXFP4 weight-only projections (with quant_mxfp4.hip) ---------
 int cake_gemv_w4_set_tuning(int kind, int U, int prefetch, int max_blocks);
 int cake_gemv_w4_get_tuning(int kind, int* out3);

@@ -125,6 +125,12 @@ const Flag kFlags[] = {
      "in consecutive windows of --max-seq-len, teacher forced; one JSON line {tokens, scored, "
      "windows, nll, ppl, top1} on stdout (any --weight-dtype / --head-dtype / --kv-dtype / "
      "--prefill-dtype; not with --parallel tp)"},
+    {"--prompts-file", "prompts_file", PyArg::kStr, nullptr, nullptr, false,
+     "native Llama engine: decode the 1..8 lines of this UTF-8 text file as one lock-step "
+     "batch, each line treated as --prompt treats its text (sequence i draws with --seed + i); "
+     "one JSON line per prompt {index, n_prompt, tokens, text} on stdout (16-bit weights, "
+     "lm_head and KV cache on one GPU; not with --parallel tp, a pipeline, topology workers, "
+     "--logprobs-file or the logit-control flags)"},
     {"--logprobs-file", "logprobs_file", PyArg::kStr, nullptr, nullptr, false,
      "native Llama engine: write one JSON line per generated token to PATH: {index, id, logprob, "
      "top_ids, top_logprobs}, over the logits token selection saw (after the repeat penalty, "
@@ -201,6 +207,7 @@ struct EngineApi {
   decltype(&cake_engine_open_remote) open_remote;
   decltype(&cake_engine_serve) serve;
   decltype(&cake_engine_generate) generate;
+  decltype(&cake_engine_generate_batch) generate_batch;
   decltype(&cake_engine_score) score;
   decltype(&cake_engine_set_logprobs) set_logprobs;
   decltype(&cake_engine_logprobs) logprobs;
@@ -379,6 +386,35 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
                          "--logit-bias apply to generation, not to --score-file\n");
     return 2;
   }
+  const bool batching = o["prompts_file"].kind != PyArg::kNone;
+  if (batching) {  // refused where the engine's generate_batch is, before the library loads
+    const char* why = nullptr;
+    std::string fmt_why;
+    if (o["transport"].value == "rccl")
+      why = "--prompts-file is not supported with --transport rccl: a pipeline or "
+            "tensor-parallel engine does not batch sequences";
+    else if (scoring) why = "--prompts-file and --score-file exclude each other";
+    else if (lp_on) why = "--prompts-file does not record logprobs: drop --logprobs-file";
+    else if (lc.any)
+      why = "--prompts-file does not apply --presence-penalty / --frequency-penalty / --min-p / "
+            "--logit-bias";
+    else if (topo && !topo->nodes.empty())
+      why = "--prompts-file is not supported with topology workers: an engine with remote "
+            "workers does not batch sequences";
+    else
+      for (const char* k : {"weight_dtype", "head_dtype", "kv_dtype", "prefill_dtype"})
+        if (!why && o[k].value != "model") {
+          std::string flag = std::string("--") + k;
+          flag[flag.find('_')] = '-';
+          fmt_why = "--prompts-file runs 16-bit weights, lm_head and KV cache: not with " + flag +
+                    " " + o[k].value;
+          why = fmt_why.c_str();
+        }
+    if (why) {
+      std::fprintf(stderr, "cake-cli: %s\n", why);
+      return 2;
+    }
+  }
   const std::string lib = cake::package_root() + "/cake_amd/lib/libcake_engine.so";
   void* h = dlopen(lib.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!h) {
@@ -388,6 +424,8 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   EngineApi api{};
   api.open = reinterpret_cast<decltype(api.open)>(dlsym(h, "cake_engine_open"));
   api.generate = reinterpret_cast<decltype(api.generate)>(dlsym(h, "cake_engine_generate"));
+  api.generate_batch =
+      reinterpret_cast<decltype(api.generate_batch)>(dlsym(h, "cake_engine_generate_batch"));
   api.close = reinterpret_cast<decltype(api.close)>(dlsym(h, "cake_engine_close"));
   api.open_pp = reinterpret_cast<decltype(api.open_pp)>(dlsym(h, "cake_engine_open_pp"));
   api.serve = reinterpret_cast<decltype(api.serve)>(dlsym(h, "cake_engine_serve"));
@@ -401,7 +439,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
       dlsym(h, "cake_engine_set_logit_controls"));
   if (!api.open || !api.generate || !api.close || !api.open_pp || !api.serve || !api.open_tp ||
       !api.open_remote || !api.score || !api.set_logprobs || !api.logprobs ||
-      !api.set_logit_controls) {
+      !api.set_logit_controls || !api.generate_batch) {
     std::fprintf(stderr, "cake-cli: engine symbols missing in %s\n", lib.c_str());
     return 1;
   }
@@ -452,6 +490,7 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     return rc ? 1 : 0;
   }
   std::vector<std::pair<int32_t, int32_t>> windows;  // --score-file: [start, end) token runs
+  std::vector<int32_t> batch_off;                    // --prompts-file: prompt b = ids[off[b], off[b + 1])
   if (scoring) {
     try {
       cake::Json req = cake::Json::object();
@@ -468,6 +507,24 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
     } catch (const std::exception& e) {
       std::fprintf(stderr, "cake-cli: --score-file: %s\n", e.what());
       return 1;
+    }
+  } else if (batching) {
+    try {
+      cake::Json req = cake::Json::object();
+      req.set("model", cake::Json::string(ctx.model));
+      req.set("system", cake::Json::string(o["system_prompt"].value));
+      req.set("path", cake::Json::string(o["prompts_file"].value));
+      const cake::Json r = cake::Json::parse(
+          cake::call_python("cake_amd.native_bridge", "encode_prompts_file", req.dump()));
+      batch_off.push_back(0);
+      for (const auto& p : r.get("prompts").items()) {
+        for (const auto& x : p.items()) ids.push_back((int32_t)x.as_int());
+        batch_off.push_back((int32_t)ids.size());
+      }
+      for (const auto& x : r.get("eos").items()) ctx.eos.push_back((int32_t)x.as_int());
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "cake-cli: --prompts-file: %s\n", e.what());
+      return 2;
     }
   } else
   try {
@@ -576,6 +633,54 @@ int run_native_text(cake::PyArgs& o, const cake::Topology* topo) {
   smp.repeat_penalty = (float)num("repeat_penalty", 1.1);
   smp.repeat_last_n = (int32_t)num("repeat_last_n", 128);
   const int32_t n = (int32_t)num("sample_len", 100);
+  if (batching) {  // one lock-step batch; one JSON line per prompt
+    const int32_t B = (int32_t)batch_off.size() - 1;
+    int32_t longest = 0;
+    for (int32_t b = 0; b < B; ++b) longest = std::max(longest, batch_off[b + 1] - batch_off[b]);
+    const int32_t max_new = std::min(n, eo.max_seq - longest);
+    if (max_new <= 0) {
+      std::fprintf(stderr, "cake-cli: prompt does not fit the KV cache (--max-seq-len)\n");
+      api.close(eng);
+      return 1;
+    }
+    std::vector<int32_t> out((size_t)B * max_new), out_len((size_t)B);
+    CakeEngineStats st{};
+    if (api.generate_batch(eng, ids.data(), batch_off.data(), B, max_new, &smp, ctx.eos.data(),
+                           (int32_t)ctx.eos.size(), out.data(), out_len.data(), nullptr, &st,
+                           nullptr, err, sizeof(err))) {
+      std::fprintf(stderr, "cake-cli: native engine: %s\n", err);
+      api.close(eng);
+      return 1;
+    }
+    api.close(eng);
+    try {
+      cake::Json req = cake::Json::object(), ps = cake::Json::array(), ts = cake::Json::array(),
+                 es = cake::Json::array();
+      for (int32_t b = 0; b < B; ++b) {
+        cake::Json p = cake::Json::array(), t = cake::Json::array();
+        for (int32_t i = batch_off[b]; i < batch_off[b + 1]; ++i) p.push(cake::Json::integer(ids[i]));
+        for (int32_t i = 0; i < out_len[b]; ++i)
+          t.push(cake::Json::integer(out[(size_t)b * max_new + i]));
+        ps.push(p);
+        ts.push(t);
+      }
+      for (int32_t e : ctx.eos) es.push(cake::Json::integer(e));
+      req.set("model", cake::Json::string(ctx.model));
+      req.set("prompts", ps);
+      req.set("tokens", ts);
+      req.set("eos", es);
+      std::printf("%s\n", cake::call_python("cake_amd.native_bridge", "prompts_result_lines",
+                                            req.dump()).c_str());
+      std::fflush(stdout);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "cake-cli: tokenizer: %s\n", e.what());
+      return 1;
+    }
+    std::fprintf(stderr, "[cake-cli] %d tokens generated in %d sequences (%.2f token/s together) "
+                 "p50=%.2fms p99=%.2fms per step\n", st.n_generated, B, st.tokens_per_s, st.p50_ms,
+                 st.p99_ms);
+    return 0;
+  }
   const int32_t room = eo.max_seq - (int32_t)ids.size() - 3;
   const int32_t max_new = n < room ? n : room;
   std::vector<int32_t> out((size_t)(max_new > 0 ? max_new : 1));

@@ -111,6 +111,12 @@ def _bind(L) -> None:
                                        C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
                                        C.c_char_p, I]
     L.cake_engine_generate.restype = I
+    L.cake_engine_generate_batch.argtypes = [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), I, I,
+                                             C.POINTER(EngineSampling), C.POINTER(C.c_int32), I,
+                                             C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                             C.POINTER(EngineStats), C.POINTER(EngineStats),
+                                             C.POINTER(C.c_float), C.c_char_p, I]
+    L.cake_engine_generate_batch.restype = I
     L.cake_engine_continue.argtypes = [P, I, C.POINTER(C.c_int32), I, TOKEN_CB, P,
                                        C.POINTER(C.c_int32), I, C.POINTER(EngineStats),
                                        C.c_char_p, I]
@@ -159,6 +165,10 @@ class GenResult:
     p50_ms: float = 0.0
     p99_ms: float = 0.0
     logprobs: "TokenLogprobs | None" = None   # generate(..., logprobs=K)
+    logits: "object | None" = None   # generate_batch(..., return_logits=True): f32 [tokens, V]
+
+
+MAX_BATCH = 8   # prompts of one generate_batch call (llama_engine.h)
 
 
 LOGPROBS_MAX_TOP = 20
@@ -566,6 +576,58 @@ class NativeLlama:
         return self._run(lambda eos_arr, n_eos, cb, out, stats, err: lib().cake_engine_generate(
             self._h, arr, len(prompt), int(max_new), C.byref(smp), eos_arr, n_eos, cb, None, out,
             max(1, max_new), stats, err, len(err)), max_new, eos_ids, on_token)
+
+    def generate_batch(self, prompts: list[list[int]], max_new: int, *, temperature: float = 0.0,
+                       top_k: int | None = None, top_p: float | None = None,
+                       seed: int = 299792458, repeat_penalty: float = 1.1,
+                       repeat_last_n: int = 128, eos_ids: list[int] | None = None,
+                       return_logits: bool = False) -> list[GenResult]:
+        """Lock-step batched decode of 1..8 prompts: one pass over the weights per step for all
+        of them.  One sampling setting; sequence ``b`` draws with ``seed + b``, and its tokens
+        are bit for bit those of ``generate_batch([prompts[b]], ..., seed=seed + b)``.  A
+        sequence ends at its first EOS (inclusive).  ``return_logits``: each result carries the
+        f32 rows token selection saw, ``[len(tokens), V]`` (tests).  The times and the step
+        percentiles of every result are the call's; ``tokens_per_s`` is the sequence's own.
+        The engine refuses (``RuntimeError``) what it does not batch: pipeline, tensor-parallel,
+        remote and layers-only engines, quantised weights / lm_head / KV cache, log-probs or
+        logit controls left on by a previous :meth:`generate`, more than 8 or no prompts, an
+        empty prompt, ``len(prompt) + max_new > max_seq``."""
+        import numpy as np
+        B = len(prompts)
+        flat = [int(t) for p in prompts for t in p]
+        offs = [0]
+        for p in prompts:
+            offs.append(offs[-1] + len(p))
+        tok_arr = (C.c_int32 * max(1, len(flat)))(*flat)
+        off_arr = (C.c_int32 * (B + 1))(*offs)
+        eos = list(eos_ids or [])
+        eos_arr = (C.c_int32 * max(1, len(eos)))(*eos)
+        n_out = max(1, B) * max(1, int(max_new))
+        out = (C.c_int32 * n_out)()
+        out_len = (C.c_int32 * max(1, B))()
+        seq_stats = (EngineStats * max(1, B))()
+        smp = EngineSampling(float(temperature or 0.0), int(top_k or 0), float(top_p or 0.0),
+                             int(seed) & 0xFFFFFFFFFFFFFFFF, float(repeat_penalty),
+                             int(repeat_last_n))
+        logits = None
+        if return_logits and 1 <= B <= MAX_BATCH and max_new > 0:
+            logits = np.empty((B, int(max_new), self.vocab_size), dtype=np.float32)
+        err = C.create_string_buffer(1024)
+        rc = lib().cake_engine_generate_batch(
+            self._h, tok_arr, off_arr, B, int(max_new), C.byref(smp), eos_arr, len(eos), out,
+            out_len, seq_stats, None,
+            None if logits is None else logits.ctypes.data_as(C.POINTER(C.c_float)), err, len(err))
+        if rc:
+            raise RuntimeError(f"native engine: {err.value.decode(errors='replace')}")
+        res = []
+        for b in range(B):
+            s, n = seq_stats[b], int(out_len[b])
+            r = GenResult([int(out[b * int(max_new) + i]) for i in range(n)], s.n_prompt,
+                          s.prefill_s, s.decode_s, s.tokens_per_s, s.p50_ms, s.p99_ms)
+            if logits is not None:
+                r.logits = logits[b, :n]
+            res.append(r)
+        return res
 
     def set_logprobs(self, k: int | None) -> None:
         """The log-prob setting of the next :meth:`generate` (None: off, 0..20: on)."""

@@ -175,6 +175,58 @@ class NativeLLM(TextGenerator):
         return out
 
 
+    # ------------------------------------------------------------------ batched decode
+    def batch_refusal(self) -> str | None:
+        """Why this engine cannot run :meth:`generate_n` / ``generate_batch``, or None: known
+        before any work is queued (the engine call refuses the same things)."""
+        e = self.eng
+        if getattr(e, "tp", False):
+            return "a tensor-parallel engine does not batch sequences"
+        if getattr(e, "world", 1) > 1:
+            return "a pipeline engine does not batch sequences"
+        if getattr(e, "_remote", None) is not None:
+            return "an engine with remote workers does not batch sequences"
+        fmts = [f"{k} {getattr(e, a)}" for k, a in (("weights", "weights"), ("lm_head", "head"),
+                                                     ("KV cache", "kv"))
+                if getattr(e, a, "model") != "model"]
+        if fmts:
+            return "batched decode runs 16-bit weights, lm_head and KV cache, not " + ", ".join(fmts)
+        return None
+
+    def _batch_kw(self) -> dict:
+        s = self.sampling
+        return dict(temperature=0.0 if s.greedy else float(s.temperature), top_k=s.top_k,
+                    top_p=s.top_p, seed=int(s.seed), repeat_penalty=float(s.repeat_penalty),
+                    repeat_last_n=int(s.repeat_last_n))
+
+    def text_of(self, tokens: list[int]) -> str:
+        """The text a generation of these tokens streams: every token's own decoding, the
+        EOS left out."""
+        return "".join(str(self._token(t)) for t in tokens if t not in self.eos_ids)
+
+    def generate_n(self, n: int, max_tokens: int) -> list[tuple[str, int]]:
+        """``n`` completions of the chat prompt on one lock-step batch (REST ``n``): choice i
+        draws with seed + i.  [(text, generated tokens)]."""
+        prompt = self._prompt()
+        room = self.eng.max_seq - len(prompt)
+        if room <= 0:
+            raise RuntimeError("prompt does not fit the KV cache (--max-seq-len)")
+        self.eng.set_logprobs(None)
+        self.eng.set_logit_controls(None)
+        res = self.eng.generate_batch([prompt] * n, min(max_tokens, room),
+                                      eos_ids=sorted(self.eos_ids), **self._batch_kw())
+        self.last_result = res[0]
+        self.generated = sum(len(r.tokens) for r in res)
+        return [(self.text_of(r.tokens), len(r.tokens)) for r in res]
+
+    def generate_prompts(self, prompts: list[list[int]], max_tokens: int) -> list[list[int]]:
+        """``--prompts-file``: the tokens of 1..8 tokenised prompts decoded as one batch."""
+        res = self.eng.generate_batch(prompts, max_tokens, eos_ids=sorted(self.eos_ids),
+                                      **self._batch_kw())
+        self.last_result = res[0]
+        return [r.tokens for r in res]
+
+
 def score_file(ctx, path: str) -> dict:
     """``--score-file``: teacher-forced log-likelihood of a text file on the native engine,
     in windows of ``--max-seq-len`` tokens (native_bridge.score_windows); the result line's

@@ -48,6 +48,53 @@ def decode_token(req: str) -> str:
         return ""
 
 
+PROMPTS_FILE_MAX = 8   # lines of a --prompts-file: the engine's lock-step batch
+
+
+def read_prompts_file(path: str) -> list[str]:
+    """The prompts of a ``--prompts-file``: 1..8 lines of UTF-8 text, none empty (a final
+    newline is not a line).  ValueError otherwise."""
+    lines = Path(path).read_text(encoding="utf-8").split("\n")
+    if lines and lines[-1] == "":
+        lines.pop()
+    lines = [ln.rstrip("\r") for ln in lines]
+    if not 1 <= len(lines) <= PROMPTS_FILE_MAX:
+        raise ValueError(f"--prompts-file takes 1 to {PROMPTS_FILE_MAX} lines, {path} has "
+                         f"{len(lines)}")
+    for i, ln in enumerate(lines):
+        if not ln.strip():
+            raise ValueError(f"--prompts-file: line {i + 1} of {path} is empty")
+    return lines
+
+
+def encode_prompts_file(req: str) -> str:
+    """{"model", "system", "path"} -> {"prompts": [[ids], ...], "eos": [...]}: every line
+    rendered and tokenised as ``--prompt`` is (encode_chat)."""
+    r = json.loads(req)
+    out, eos = [], []
+    for line in read_prompts_file(r["path"]):
+        one = json.loads(encode_chat(json.dumps({"model": r["model"], "system": r.get("system", ""),
+                                                 "prompt": line})))
+        out.append(one["ids"])
+        eos = one["eos"]
+    return json.dumps({"prompts": out, "eos": eos})
+
+
+def prompts_result_lines(req: str) -> str:
+    """{"model", "prompts": [[ids], ...], "tokens": [[ids], ...], "eos": [...]} -> the result
+    lines of ``--prompts-file``, one JSON object per prompt: index, n_prompt, tokens, text
+    (every token's own decoding, an EOS left out)."""
+    r = json.loads(req)
+    eos = set(r.get("eos", []))
+    lines = []
+    for i, (p, toks) in enumerate(zip(r["prompts"], r["tokens"])):
+        text = "".join(decode_token(json.dumps({"model": r["model"], "id": t}))
+                       for t in toks if t not in eos)
+        lines.append(json.dumps({"index": i, "n_prompt": len(p), "tokens": list(toks),
+                                 "text": text}))
+    return "\n".join(lines)
+
+
 def score_windows(n_tokens: int, max_seq: int) -> list[tuple[int, int]]:
     """[start, end) of the windows ``--score-file`` scores: consecutive runs of ``max_seq``
     tokens, each scored from position 0 (its first token unscored); a last window of one

@@ -114,6 +114,12 @@ _SIGS = {
     # kernels/gemv_p13_mlp.hip
     "cake_swiglu_p13": (I, [I, P, P, F, P, P, P, P, P, P, I, I, P, P]),
     "cake_gemv_x16_p13": (I, [I, P, P, P, P, I, I, P, I, P]),
+    # kernels/gemv_rows.hip: the projections of a lock-step batched decode step
+    "cake_gemv_rows_set_tuning": (I, [I, I, I, I]),
+    "cake_gemv_rows_get_tuning": (I, [I, P]),
+    "cake_gemv_rows": (I, [I, I, P, L, P, L, P, L, P, L, I, I, I, P]),
+    "cake_rmsnorm_split_rows": (I, [I, P, P, F, I, I, P, P]),
+    "cake_rope_kv_rows": (I, [I, P, L, I, P, P, I, I, I, I, P, P, P, L, P]),
     # kernels/gemv_w4.hip: MXFP4 weight-only projections (with quant_mxfp4.hip
     "cake_gemv_w4_set_tuning": (I, [I, I, I, I]),
     "cake_gemv_w4_get_tuning": (I, [I, P]),

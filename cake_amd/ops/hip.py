@@ -790,6 +790,108 @@ def set_gemv_tuning(kind: str, U: int = 4, prefetch: int = 0, max_blocks: int = 
 
 
 # ---------------------------------------------------------------------------
+# Lock-step batched decode (gemv_rows.hip): projections of 1..16 activation rows on one weight
+# stream, and the per-row RoPE / KV write.  M, K and the strides are judged by the library (a
+# call it refuses raises KernelError); the wrappers check that every tensor covers its shape.
+# ---------------------------------------------------------------------------
+
+GEMV_ROWS_EPI = {"store32": 6, "resid32": 1, "swiglu": 3}   # cake::GemmEpi ids
+
+
+def set_gemv_rows_tuning(epi: str, tiles: int = 2, unroll: int = 4, max_blocks: int = 4096) -> None:
+    """Launch geometry of one gemv_rows epilogue: row tiles per workgroup (1, 2 or 4; swiglu 1
+    or 2; halved by the launcher while the grid would stay below 512 workgroups), k steps per
+    trip (2 or 4) and the grid cap."""
+    check(kernels().cake_gemv_rows_set_tuning(GEMV_ROWS_EPI[epi], int(tiles), int(unroll),
+                                              int(max_blocks)), "gemv_rows_set_tuning")
+
+
+def get_gemv_rows_tuning(epi: str) -> tuple[int, int, int]:
+    out = (C.c_int * 3)()
+    check(kernels().cake_gemv_rows_get_tuning(GEMV_ROWS_EPI[epi], out), "gemv_rows_get_tuning")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _view2(t: torch.Tensor, name: str, rows: int, cols: int, dtype) -> int:
+    """Validate a [>= rows, cols] row-strided device view; return its row stride."""
+    if not t.is_cuda or t.dtype != dtype or t.dim() != 2 or t.shape[0] < rows \
+            or t.shape[1] != cols or (cols > 1 and t.stride(1) != 1) or t.stride(0) < cols:
+        raise ValueError(f"{name}: expected a [>= {rows}, {cols}] {dtype} device view with unit "
+                         f"column stride, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    return t.stride(0)
+
+
+def gemv_rows(x, w, out, epi: str = "store32", M: int | None = None):
+    """Rows [0, M) of x [*, K] (16-bit) times w [N, K]^T on one pass over w, 1 <= M <= 16.
+
+    store32: out f32 [*, N] = x w^T.  resid32: out f32 [*, N] += x w^T.  swiglu: w is the packed
+    gate | up [2 I, K] and out 16-bit [*, I] = silu(x gate^T) * (x up^T).  Rows >= M of out are
+    not written."""
+    if epi not in GEMV_ROWS_EPI:
+        raise ValueError(f"gemv_rows: unknown epilogue {epi!r}")
+    M = x.shape[0] if M is None else int(M)
+    K = x.shape[1]
+    _req(w, "w", dtype=x.dtype)
+    if w.dim() != 2 or w.shape[1] != K:
+        raise ValueError(f"w: expected [N, {K}], got {tuple(w.shape)}")
+    N = w.shape[0]
+    if epi == "swiglu":
+        if N % 2:
+            raise ValueError("gemv_rows swiglu: w must be the packed gate | up [2 I, K]")
+        N //= 2
+    rows = max(M, 0)
+    ldx = _view2(x, "x", rows, K, w.dtype)
+    ldo = _view2(out, "out", rows, N, w.dtype if epi == "swiglu" else torch.float32)
+    r32 = epi == "resid32"
+    check(kernels().cake_gemv_rows(_dt(w), GEMV_ROWS_EPI[epi], _p(x), ldx, _p(w), K,
+                                   None if r32 else _p(out), ldo, _p(out) if r32 else None, ldo,
+                                   M, N, K, _stream()), "gemv_rows")
+    return out
+
+
+def rmsnorm_split_rows(x, w, eps, out):
+    """RMSNorm of x f32 [M, H], M <= 8, as two 16-bit terms: out [2M, H], row m what
+    :func:`rmsnorm` writes, row M + m the rounded remainder of the f32 value."""
+    M, H = x.shape
+    _req(x, "x", dtype=torch.float32)
+    _req(w, "w", shape=(H,))
+    _req(out, "out", dtype=w.dtype, shape=(2 * M, H))
+    check(kernels().cake_rmsnorm_split_rows(_dt(w), _p(x), _p(w), float(eps), M, H, _p(out),
+                                            _stream()), "rmsnorm_split_rows")
+    return out
+
+
+def rope_kv_rows(qkv32, pos, inv_freq, q_out, kcaches, vcaches, layer: int = 0):
+    """Per-row twin of the decode QKV epilogue.  qkv32 f32 [M, (nh + 2 nkv) hd]; pos int32 [M];
+    kcaches / vcaches: M 16-bit caches [L, nkv, S, hd], one per row (a cache may repeat only
+    where the positions differ).  q_out f32 [M, nh hd] receives the roped q; k roped and v are
+    rounded once into row pos[m] of layer `layer` of cache m.  A row whose position is outside
+    [0, S) writes nothing."""
+    M = qkv32.shape[0]
+    if len(kcaches) != M or len(vcaches) != M:
+        raise ValueError(f"rope_kv_rows: {M} rows need {M} k and v caches")
+    L, nkv, S, hd = kcaches[0].shape
+    if not 0 <= layer < L:
+        raise ValueError(f"rope_kv_rows: layer {layer} outside [0, {L})")
+    dt = kcaches[0].dtype
+    for c in (*kcaches, *vcaches):
+        _req(c, "cache", dtype=dt, shape=(L, nkv, S, hd))
+    nh = q_out.shape[1] // hd
+    ldq = _view2(qkv32, "qkv32", M, (nh + 2 * nkv) * hd, torch.float32)
+    _req(q_out, "q_out", dtype=torch.float32, shape=(M, nh * hd))
+    _req(pos, "pos", dtype=torch.int32, shape=(M,))
+    _req(inv_freq, "inv_freq", dtype=torch.float32, shape=(hd // 2,))
+    dev = qkv32.device
+    kb = torch.tensor([c.data_ptr() for c in kcaches], dtype=torch.int64, device=dev)
+    vb = torch.tensor([c.data_ptr() for c in vcaches], dtype=torch.int64, device=dev)
+    check(kernels().cake_rope_kv_rows(_DT[dt], _p(qkv32), ldq, M, _p(pos), _p(inv_freq), nh, nkv,
+                                      hd, S, _p(q_out), _p(kb), _p(vb), layer * nkv * S * hd,
+                                      _stream()), "rope_kv_rows")
+    kb.record_stream(torch.cuda.current_stream())
+    vb.record_stream(torch.cuda.current_stream())
+
+
+# ---------------------------------------------------------------------------
 # FP8 (OCP e4m3fn) weight-only projections: w8 [N, K] uint8 codes + scale [N] f32,
 # W[n, k] = scale[n] * fp8(w8[n, k]); K % 16 == 0 (quant_fp8.hip, gemv_w8*.hip).
 # The oracle is ops/reference.py quant_rows_fp8 / dequant_rows_fp8.
